@@ -23,7 +23,13 @@ sharded: count k = 8 with dedupe, count k = 14, scan k = 8 r = 2 -- ms per pass 
 roofline fraction) and `e2e` (BOTH VERBS on a clean C3 res_dir under the process group, SEQ default and FAST: north_star's metric).
 `--shard-proxy G` (N = 1): every rank's share of a G-GPU run timed on the one GPU, shard after shard (`shard_proxy`).
 
-Extra objects on the JSON line:
+A plain run (`--gpus G --steps K --warmup W`) does only what the headline needs: `scan_motif` on the C3 reads (the sample above;
+`visualize_kmers` runs with --full only), the clock ramp and W warm-up steps, the K timed steps, the optional output dump, and the
+line with the contract keys, `config` and `roofline` from the timed steps' events.  `--full` adds everything else: the oracle spot-check of the timed rows, the device-fill ceiling
+(`frac_of_achievable`), the rank identities, every leg below and the detail file.  `--dump-outputs DIR` writes a fixed, seeded sample
+of rows of the last timed step's matrix to DIR (float32), so that two builds can be compared output for output.
+
+Extra objects on the JSON line (all but `roofline` with --full only):
   roofline      HIP-event kernel time of the headline kernel (mean / min / median per launch) vs the 8 TB/s HBM peak, algorithmic
                 bytes = rows*N + 5N; `frac_of_achievable` = the same against a plain device fill of the same bytes measured in
                 this run on this box; `stages`: the same for every other stage of the C3 path with SURVEY 8(d)'s bytes
@@ -56,6 +62,28 @@ N_C4 = 200_000
 
 
 # ---- the sample the C3 pipeline hands over ------------------------------------------------------------------------------
+def c3_hand_over(reads):
+    """The C3 res_dir as run_e2e("C3", "default") leaves it after its first verb: the inputs written with the same overrides, then
+    scan_motif alone after the same np.random.seed(123), so its sample_kmers.pkl is the full run's.  Returns the directory (the
+    caller removes it)."""
+    import contextlib
+    import io
+    import tempfile
+    from kmap_amd import motif_discovery as md, synth
+    from kmap_amd.e2e import CONFIGS
+    c = CONFIGS["C3"]
+    res = Path(tempfile.mkdtemp(prefix="kmap_C3_"))
+    over = {"kmer_count": {"min_k": 6, "max_k": 9},
+            "motif_discovery": {"motif_pos_density_flag": False, "motif_co_occurence_flag": False, "gen_hamball_flag": False,
+                                "n_total_sample": c["n_total"], "n_motif_sample": c["n_motif"]},
+            "visualization": {"gen_fig_flag": False, "random_seed": 7, "n_max_iter": c["iters"]}}
+    synth.write_res_dir(res, reads[0], reads[1], over)
+    with contextlib.redirect_stdout(io.StringIO()):
+        np.random.seed(123)
+        md._scan_motif(str(res))
+    return str(res)
+
+
 def pipeline_sample(res_dir, n_total):
     """Expanded (hashes uint32, labels int32, consensus lengths) of `n_total` sampled k-mers drawn by sample_disp_kmer from the
     kept C3 result directory (n_total = the run's own n_total_sample re-uses its sample_kmers.pkl)."""
@@ -90,6 +118,7 @@ def ramp(fn, min_ms=RAMP_MS, max_calls=2000):
     timed region (no host synchronisation in between), so that the timed launches run at the clocks a real job -- thousands
     of launches -- runs at.  Returns the number of extra launches."""
     from kmap_amd import _ffi
+    fn()                # the first launch in a process also loads the kernels' code: its time would shorten the ramp
     e0, e1 = _ffi.Event(), _ffi.Event()
     e0.record()
     fn()
@@ -99,7 +128,7 @@ def ramp(fn, min_ms=RAMP_MS, max_calls=2000):
     calls = int(min(max_calls, max(1, math.ceil(min_ms / one))))
     for _ in range(calls):
         fn()
-    return calls + 1
+    return calls + 2
 
 
 def timed_launches(fn, reps, warmup=2):
@@ -892,6 +921,26 @@ def fill_rate(nbytes, reps=7):
             "what": "hipMemsetAsync of the same byte count, HIP events, same stream, same run"}
 
 
+DUMP_LIMIT = 64 << 20   # bytes: what --dump-outputs writes in all
+
+
+def dump_rows(n, seed=0):
+    """the fixed, seeded sample of rows of the N x N matrix that --dump-outputs writes: as many whole rows as fit DUMP_LIMIT in
+    float32 (at most 256), drawn without replacement, ascending"""
+    count = min(n, 256, (DUMP_LIMIT - (1 << 20)) // (4 * n))
+    return np.sort(np.random.default_rng(seed).choice(n, size=count, replace=False))
+
+
+def write_outputs(out_dir, rows, mat):
+    """DIR/hamming_rows.npy: the sampled rows of the timed matrix (float32; distances <= k are exact), DIR/hamming_row_index.npy:
+    their row numbers (float64)"""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "hamming_rows.npy", mat.astype(np.float32))
+    np.save(out / "hamming_row_index.npy", np.asarray(rows, np.float64))
+    assert sum(f.stat().st_size for f in (out / "hamming_rows.npy", out / "hamming_row_index.npy")) <= DUMP_LIMIT
+
+
 LINE_LIMIT = 4096       # bytes: the one JSON line on stdout never exceeds this (asserted before it is written)
 T_START = time.perf_counter()
 
@@ -998,11 +1047,12 @@ def write_detail(line, world):
         return None
 
 
-def emit(fd, line, world):
-    """detail file + stderr summary, then the compact line to the saved stdout descriptor"""
-    rel = write_detail(line, world)
+def emit(fd, line, world, detail=True):
+    """detail file (--full runs) + stderr summary, then the compact line to the saved stdout descriptor"""
+    rel = write_detail(line, world) if detail else None
     text = compact_line(line, rel)
-    print(f"bench.py: full record in {rel} ({(ROOT / rel).stat().st_size if rel else 0} bytes); line {len(text)} bytes", file=sys.stderr, flush=True)
+    if rel:
+        print(f"bench.py: full record in {rel} ({(ROOT / rel).stat().st_size} bytes); line {len(text)} bytes", file=sys.stderr, flush=True)
     os.write(fd, (text + "\n").encode())
 
 
@@ -1150,7 +1200,15 @@ def main():
     ap.add_argument("--no-stages", action="store_true", help="skip the per-stage roofline timings")
     ap.add_argument("--e2e", default="full", choices=["none", "k9", "full"],
                     help="end-to-end timings on C3 (rank 0, N=1 only): k9 = k 6..9 in both embedding modes; full = also the default k 6..16")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the oracle spot-check of the timed rows, the device-fill ceiling, the rank identities, "
+                         "the optional legs above (under --time-budget) and the detail file; without it a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed, seeded sample of rows of the last step's Hamming matrix to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
 
@@ -1166,7 +1224,10 @@ def main():
     if world != args.gpus:
         args.gpus = world
 
-    import torch
+    # a plain run on one GPU needs no torch: the headline kernel runs on the library's own stream
+    torch = None
+    if args.full or world > 1:
+        import torch
     from kmap_amd import _ffi
     from kmap_amd.e2e import run_e2e, synth_config_reads
     from kmap_amd.hamdist import hamdist_matrix_dev, pitch_for
@@ -1176,7 +1237,8 @@ def main():
     dev = 0 if os.environ.get("KMAP_BENCH_SAME_GPU") else local_rank
     if os.environ.get("KMAP_BENCH_SAME_GPU"):
         os.environ["KMAP_DIST_SAME_GPU"] = "1"      # the verbs of the e2e leg pick their device the same way
-    torch.cuda.set_device(dev)
+    if torch is not None:
+        torch.cuda.set_device(dev)
     _ffi.check(_ffi.lib().kmap_set_device(dev))
     dist = None
     if world > 1:
@@ -1189,18 +1251,24 @@ def main():
     def barrier():
         if dist is not None:
             _barrier(dist, torch)
-        torch.cuda.synchronize()
+        if torch is not None:
+            torch.cuda.synchronize()
         _ffi.sync()
 
-    # ---- the C3 pipeline (rank 0): its hand-over is the workload of the timed kernel; its wall time is e2e["k6_9"]["default"] ----
+    # ---- the C3 pipeline (rank 0): its hand-over is the workload of the timed kernel; with --full the whole run, whose wall time
+    # is e2e["k6_9"]["default"], otherwise scan_motif alone (the same hand-over) ----
     n = int(round(N_BASE * math.sqrt(world) / 16)) * 16
     reads, first, res_dir = None, None, None
     if rank == 0:
         os.environ["KMAP_DIST_DISABLE"] = "1"       # rank 0 runs the pipeline on its own GPU; the verbs must not join the process group
         reads = synth_config_reads("C3")
-        first = run_e2e("C3", "default", reads=reads, keep=True)
+        if args.full:
+            first = run_e2e("C3", "default", reads=reads, keep=True)
+            res_dir = first["res_dir"]
+        else:
+            res_dir = c3_hand_over(reads)
+            reads = None
         os.environ.pop("KMAP_DIST_DISABLE")
-        res_dir = first["res_dir"]
         kh, lab, lens, conseqs = pipeline_sample(res_dir, n)
         s50 = (kh, lab, lens, conseqs) if n == N_BASE else pipeline_sample(res_dir, N_BASE)
         c3s = (s50[0], s50[1], s50[3])              # the C3 hand-over itself, N = 50 000 (the strong-scaling embedding leg)
@@ -1241,19 +1309,30 @@ def main():
         wall = float(t.item())
 
     # spot-check the timed output against the oracle (a wrong fast kernel is not a result): rows of every label
-    from oracle import oracle as O
-    if nrows:
+    if args.full and nrows:
+        from oracle import oracle as O
         picks = sorted({row0, row0 + nrows // 2, row0 + nrows - 1} | {int(np.searchsorted(lab, l)) for l in np.unique(lab) if row0 <= int(np.searchsorted(lab, l)) < row0 + nrows})
         for r in picks:
             got = out_d.to_numpy(np.uint8, (n,), offset=(r - row0) * ld)
             want = np.empty((1, n), np.uint8)
             O.lib().ko_hamdist_rows(np.ascontiguousarray(kh, np.uint64), lab, n, K, np.ascontiguousarray(lens, np.int32), len(lens), r, 1, want)
             assert np.array_equal(got, want[0]), f"timed kernel output differs from the oracle in row {r}"
+    if args.dump_outputs:
+        # a caller of the timed path receives the N x N matrix (2.5 GB at N = 50 000): a fixed, seeded sample of its rows
+        rows = dump_rows(n)
+        part = {int(r): out_d.to_numpy(np.uint8, (n,), offset=(int(r) - row0) * ld) for r in rows if row0 <= r < row0 + nrows}
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+            part = {r: v for p_ in parts for r, v in p_.items()}
+        if rank == 0:
+            write_outputs(args.dump_outputs, rows, np.stack([part[int(r)] for r in rows]))
     out_d.free()
 
-    fill = fill_rate(max(nrows, 1) * ld) if rank == 0 else None
+    fill = fill_rate(max(nrows, 1) * ld) if rank == 0 and args.full else None
 
-    ident = rank_identity(dist, torch, dev, world)      # all ranks (an all-gather of small objects, outside the timed region)
+    # all ranks (an all-gather of small objects, outside the timed region)
+    ident = rank_identity(dist, torch, dev, world) if args.full else None
     line = None
     if rank == 0:
         pairs_total = float(n) * float(n)
@@ -1272,7 +1351,7 @@ def main():
                        "sample": "sample_kmers.pkl of scan_motif on 10M x 150 bp synthetic reads (k=6..9), expanded by counts"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                         "achievable": fill, "frac_of_achievable": achieved / fill["GBps_median"],
+                         "achievable": fill, "frac_of_achievable": achieved / fill["GBps_median"] if fill else None,
                          "kernel": "hamdist_tile_kernel<1 code word> (+ build_gid / build_codes pre-passes, inside the timed region)",
                          "kernel_ms": kern_ms, "kernel_ms_min": min(per_launch), "kernel_ms_median": statistics.median(per_launch),
                          "kernel_ms_max": max(per_launch), "algorithmic_bytes": algo_bytes,
@@ -1280,8 +1359,9 @@ def main():
                                         f"the {args.warmup} warm-up steps: after an idle gap the GPU needs ~20-40 ms to restore its clocks, and the first ~40 "
                                         f"launches take 0.50 instead of 0.395 ms (tools/hamdist_trend.py, profiles/r03_hamdist_trend.txt)")},
         }
-        line.update({"ranks_seen": ident["ranks_seen"], "distinct_gpus": ident["distinct_gpus"], "dist_backend": ident["backend"],
-                     "rccl_version": ident["rccl_version"], "ranks": ident["ranks"]})
+        if ident is not None:
+            line.update({"ranks_seen": ident["ranks_seen"], "distinct_gpus": ident["distinct_gpus"], "dist_backend": ident["backend"],
+                         "rccl_version": ident["rccl_version"], "ranks": ident["ranks"]})
         # HBM bytes per launch from the PMC passes of the same command (rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE, separate
         # runs, FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes); collected offline, stored under profiles/
         pmc = sorted((ROOT / "profiles").glob("r*_bench_pmc.json"))
@@ -1293,9 +1373,10 @@ def main():
                 line["roofline"]["traffic_source"] = f"profiles/{pmc[-1].name}"
             except Exception:
                 pass
-    # ---- the optional legs (all ranks take part), most important first, under ONE deadline (Budget): a leg starts only if its
-    # expected cost still fits.  The headline above is measured and in `line`; for world > 1 a watchdog lets rank 0 print the line
-    # with what has finished if a collective never returns, instead of the whole run -- headline included -- dying at the launcher.
+    # ---- the optional legs (--full only; all ranks take part), most important first, under ONE deadline (Budget): a leg starts
+    # only if its expected cost still fits.  The headline above is measured and in `line`; for world > 1 a watchdog lets rank 0
+    # print the line with what has finished if a collective never returns, instead of the whole run -- headline included -- dying
+    # at the launcher.
     budget = Budget(args.time_budget, args.grace, world, rank, json_fd, dist, torch)
     budget.line = line
     errors = []
@@ -1325,10 +1406,10 @@ def main():
 
     G = max(world, 1)
     from kmap_amd.visualization import EMBED_SEQ
-    if line is not None and world == 1 and not args.no_cpu_baseline:
+    if args.full and line is not None and world == 1 and not args.no_cpu_baseline:
         leg("cpu_baseline", 12 if args.quick else 40, lambda: cpu_baseline(kh, lab, lens, quick=args.quick))
 
-    if dist is not None:
+    if args.full and dist is not None:
         box = [res_dir]
         dist.broadcast_object_list(box, 0)
         res_dir_all = box[0]
@@ -1363,7 +1444,7 @@ def main():
                 line["embed_dist"] = ed
             if "e2e_fast" in line:
                 line.setdefault("e2e", {}).update({k_: v for k_, v in line.pop("e2e_fast").items() if k_ in ("fast",)})
-    else:
+    elif args.full:
         if args.e2e != "none":
             # the other half of BASELINE.json's metric: end-to-end wall time on a clean res_dir (synthetic reads are generated
             # and written outside the timed stages; scan_motif loads them from the pickles like the reference)
@@ -1445,11 +1526,12 @@ def main():
     kh_d.free()
     lab_d.free()
     if rank == 0:
-        line["skipped_legs"] = budget.skipped
-        line["leg_errors"] = errors
-        line["time_budget_s"] = args.time_budget
+        if args.full:
+            line["skipped_legs"] = budget.skipped
+            line["leg_errors"] = errors
+            line["time_budget_s"] = args.time_budget
         sys.stdout.flush()
-        emit(json_fd, line, world)
+        emit(json_fd, line, world, detail=args.full)
     if res_dir:
         import shutil
         shutil.rmtree(res_dir, ignore_errors=True)

@@ -561,3 +561,24 @@ def test_bench_budget_skips_legs_that_do_not_fit(monkeypatch, capsys):
     assert not b.can("d", 0.5) and b.skipped == ["b", "d"] and b.left() < 0
     b.done()
     assert "SKIPPED" in capsys.readouterr().err
+
+
+def test_bench_output_dump_is_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: the same rows for the same N on every run, whole float32 rows within 64 MB at the one-GPU size and at
+    the eight-GPU weak-scaling size; the files are float32 (the rows) and float64 (their numbers)"""
+    import importlib
+    import sys
+    sys.path.insert(0, str(ROOT))
+    bench = importlib.import_module("bench")
+    for n in (50_000, 141_424, 100):
+        rows = bench.dump_rows(n)
+        assert np.array_equal(rows, bench.dump_rows(n)) and len(np.unique(rows)) == len(rows) > 0
+        assert rows.min() >= 0 and rows.max() < n and len(rows) * n * 4 <= bench.DUMP_LIMIT - (1 << 20)
+    rows = bench.dump_rows(100)
+    assert len(rows) == 100
+    mat = np.arange(100 * 100, dtype=np.int64).reshape(100, 100) % 9
+    bench.write_outputs(tmp_path / "d", rows, mat.astype(np.uint8))
+    got, idx = np.load(tmp_path / "d" / "hamming_rows.npy"), np.load(tmp_path / "d" / "hamming_row_index.npy")
+    assert got.dtype == np.float32 and idx.dtype == np.float64
+    np.testing.assert_array_equal(got, mat)
+    np.testing.assert_array_equal(idx, rows)
