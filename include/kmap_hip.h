@@ -307,6 +307,42 @@ int kmap_fasta_open(const char *path, kmap_fasta **f, int64_t *n_bytes, int64_t 
 int kmap_fasta_read(kmap_fasta *f, uint8_t *seq_out, int64_t *borders_out);
 int kmap_fasta_close(kmap_fasta *f);
 
+/* ---- motif locations on the genome (extract_motif_locations, util.py:292-352; csrc/host_bed.hip + csrc/locations.hip) --------
+ * Host parsers: the file is mapped and cut behind newlines into ranges that host threads parse (KMAP_IO_THREADS; KMAP_TEXT_MIN_CHUNK
+ * = smallest range in bytes, default 1 MiB); empty lines and one '\r' before a '\n' are ignored.  A malformed line -> KMAP_E_INVAL,
+ * an unreadable file -> KMAP_E_IO.
+ * Occurrence CSV `seq_ind;loc,loc;...;seq_len` as Occurrence.from_file reads it: n_cols = header fields - 2, every cell's locations
+ * sorted ascending, seq_len = int(float(cell)).  Two calls: open reports the rows, sizes the positions per column, read fills the
+ * caller's arrays (hits[c]: int32[n_rows], pos[c]: int32[n_pos[c]]). */
+typedef struct kmap_occ kmap_occ;
+int kmap_occ_open(const char *path, kmap_occ **o, int64_t *n_rows, int *n_cols);
+int kmap_occ_sizes(const kmap_occ *o, int64_t *n_pos);
+int kmap_occ_read(const kmap_occ *o, int64_t *seq_ind, int64_t *seq_len, int32_t *const *hits, int32_t *const *pos);
+int kmap_occ_close(kmap_occ *o);
+/* BED file, tab-separated, no header, 3 or 6 columns (the first line decides; any other width -> KMAP_E_INVAL).  Chrom names are
+ * interned and ranked: if every one is an integer literal (pandas reads the column as int64) by value, written in decimal, else by
+ * code point; start per row; the strand (column 6) is kept as read, "." for 3 columns. */
+typedef struct kmap_bed kmap_bed;
+int kmap_bed_open(const char *path, kmap_bed **b, int64_t *n_rows, int *n_cols, int *n_chrom, int *int_chrom);
+int kmap_bed_rows(const kmap_bed *b, int64_t *start, int32_t *chrom_rank);
+/* name of chrom rank `rank` as the output writes it (NUL-terminated); returns its length */
+int kmap_bed_chrom(const kmap_bed *b, int rank, char *buf, int cap);
+/* the output of consensus `cons_index`: "chrom\tstart\tend\tname\tscore\tstrand" header, then per entry i the line
+ * chrom(row[i]) start[i] end[i] motif_{cons_index}_{row[i]} 0 strand(row[i]), formatted on host threads like pandas
+ * to_csv(sep='\t', index=False) */
+int kmap_bed_write_locations(const kmap_bed *b, const char *path, int cons_index, int64_t n, const int64_t *row,
+                             const int64_t *start, const int64_t *end, int64_t *bytes_written);
+int kmap_bed_close(kmap_bed *b);
+/* Device pipeline (blocking; host arrays in and out): for every consensus c < n_cons and every row r with hits, the windows
+ * [bed_start[s] + p, bed_start[s] + p + cons_len[c]] of its locations p (ascending inside the cell, s = seq_ind[r]) merged where
+ * they overlap or touch, then all intervals sorted by (c, chrom_rank[s], start, end, the string "motif_c_s") on the GPU.
+ * Output: n_per_cons[c] intervals per consensus, consensus-major, as (row = s, start, end); cap >= total positions.
+ * Rows with hits must have 0 <= s < n_bed (KMAP_E_INVAL otherwise); *device_ms = upload to download, HIP events (may be NULL). */
+int kmap_locations_sort(int64_t n_rows, int n_cons, const int32_t *const *hits, const int32_t *const *pos, const int64_t *n_pos,
+                        const int32_t *cons_len, const int64_t *seq_ind, int64_t n_bed, const int64_t *bed_start,
+                        const int32_t *chrom_rank, int n_chrom, int64_t cap, int64_t *out_row, int64_t *out_start,
+                        int64_t *out_end, int64_t *n_per_cons, float *device_ms);
+
 /* ---- synthetic workload generator (benchmarks / tests; no reference operator corresponds to it): seeded reads in the array
  * contract above, generated in HBM -- BASELINE config C5 is 15 GB, minutes of numpy on the host.  Fixed-length reads, uniform
  * bases; the first fractions[0] * n_reads reads carry motif 0, the next fractions[1] * n_reads motif 1, ... at a uniform

@@ -115,6 +115,16 @@ _SIGS = {
     "kmap_fasta_open": (i32, [C.c_char_p, P(vp), P(i64), P(i64)]),
     "kmap_fasta_read": (i32, [vp, vp, vp]),
     "kmap_fasta_close": (i32, [vp]),
+    "kmap_occ_open": (i32, [C.c_char_p, P(vp), P(i64), P(i32)]),
+    "kmap_occ_sizes": (i32, [vp, vp]),
+    "kmap_occ_read": (i32, [vp, vp, vp, vp, vp]),
+    "kmap_occ_close": (i32, [vp]),
+    "kmap_bed_open": (i32, [C.c_char_p, P(vp), P(i64), P(i32), P(i32), P(i32)]),
+    "kmap_bed_rows": (i32, [vp, vp, vp]),
+    "kmap_bed_chrom": (i32, [vp, i32, C.c_char_p, i32]),
+    "kmap_bed_write_locations": (i32, [vp, C.c_char_p, i32, i64, vp, vp, vp, P(i64)]),
+    "kmap_bed_close": (i32, [vp]),
+    "kmap_locations_sort": (i32, [i64, i32, vp, vp, vp, vp, vp, i64, vp, vp, i32, i64, vp, vp, vp, vp, P(f32)]),
     "kmap_synth_reads_dev": (i32, [vp, vp, i64, i32, C.c_uint64, vp, vp, vp, i32, C.c_double, vp]),
     "kmap_hamdist_matrix_u32_dev": (i32, [vp, vp, i64, i32, vp, i32, i64, i64, vp, i64, vp]),
     "kmap_hamdist_matrix_u64_dev": (i32, [vp, vp, i64, i32, vp, i32, i64, i64, vp, i64, vp]),

@@ -1,8 +1,10 @@
 """`kmap` command line: the three verbs of the reference's CLI that sit on the GPU hot path
 (reference cli.py:9-36, kmer_count.py:70-101, motif_discovery.py:29-53, visualization.py:18-33),
-with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU).  The
-reference's plotting / alignment / reporting verbs (draw_logo, align_conseq, extract_motif_locations, plot_network,
-check_motif_co_occurence) are out of scope here.  `scan_motif` and `visualize_kmers` shard over the
+with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
+`extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
+and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
+figures).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
 
@@ -58,3 +60,30 @@ def visualize_kmers(res_dir, debug=False):
 def ex_hamball(res_dir, conseq, return_type, output_file, max_ham_dist=-1):
     from .reports import _ex_hamball
     _ex_hamball(res_dir, conseq, return_type, output_file, max_ham_dist)
+
+
+@cli.command(name="extract_motif_locations")
+@click.option("--bed_file", type=str, required=True,
+              help="Input bed file with no header, each line corresponds to each read in the input fasta file")
+@click.option("--conseq_file", type=str, default="./final_conseq.txt", required=False, help="Input conseq file")
+@click.option("--motif_occurrence_file", type=str, default="./final.motif_occurence.csv", required=False,
+              help="Input motif occurrence file")
+@click.option("--output_dir", type=str, default="./motif_locations", required=False,
+              help="Output directory for storing motif locations")
+def extract_motif_locations(bed_file, conseq_file="./final_conseq.txt", motif_occurrence_file="./final.motif_occurence.csv",
+                            output_dir="./motif_locations"):
+    from .locations import _extract_motif_locations
+    _extract_motif_locations(bed_file, conseq_file, motif_occurrence_file, output_dir)
+
+
+@cli.command(name="check_motif_co_occurence")
+@click.option("--input_fasta_file", type=str, required=True, help="Input FASTA file")
+@click.option("--motif1", type=str, required=True, help="First motif sequence")
+@click.option("--motif2", type=str, required=True, help="Second motif sequence")
+@click.option("--max_ham_dist1", type=int, required=True, help="Maximum Hamming distance for first motif")
+@click.option("--max_ham_dist2", type=int, required=True, help="Maximum Hamming distance for second motif")
+@click.option("--output_dir", type=str, required=True, help="Output directory")
+@click.option("--revcom_mode", type=bool, default=True, required=False, help="Consider reverse complements")
+def check_motif_co_occurence(input_fasta_file, motif1, motif2, max_ham_dist1, max_ham_dist2, output_dir, revcom_mode=True):
+    from .locations import check_motif_co_occurence as run
+    run(input_fasta_file, motif1, motif2, max_ham_dist1, max_ham_dist2, output_dir, revcom_mode)
