@@ -497,6 +497,8 @@ int kmap_embed_state(kmap_embed *e, int64_t *iters, int *stopped, float *last_lo
                      int *jitter_used, void *stream);
 int kmap_embed_get_coords(kmap_embed *e, float *coords_2xn, void *stream);      /* current iterate */
 int kmap_embed_get_best(kmap_embed *e, float *coords_2xn, void *stream);        /* lowest-loss snapshot */
+/* the whole best list in order (best_res_list, visualization.py:304-308): snapshots n_best x 2 x N, losses n_best (inf: a placeholder) */
+int kmap_embed_get_best_list(kmap_embed *e, float *snaps_out, float *losses_out, void *stream);
 int kmap_embed_get_losses(kmap_embed *e, float *losses, int64_t max_n, int64_t *n_out, void *stream);
 void *kmap_embed_coords_dev(kmap_embed *e);                                      /* device ptr (2 x N f32) */
 

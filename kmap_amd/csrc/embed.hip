@@ -778,6 +778,20 @@ int kmap_embed_get_best(kmap_embed *e, float *coords_2xn, void *stream) {
     return KMAP_OK;
 }
 
+int kmap_embed_get_best_list(kmap_embed *e, float *snaps_out, float *losses_out, void *stream) {
+    KMAP_REQUIRE(e && (snaps_out || losses_out), "embed_get_best_list: null");
+    KMAP_CHECK_HIP(hipStreamSynchronize(as_stream(stream)));
+    LoopState s;
+    KMAP_CHECK_HIP(hipMemcpy(&s, &e->states[e->cur], sizeof s, hipMemcpyDeviceToHost));
+    for (int b = 0; b < e->n_best; ++b) {
+        if (losses_out) losses_out[b] = s.best_loss[b];
+        if (snaps_out)
+            KMAP_CHECK_HIP(hipMemcpy(snaps_out + (size_t)b * 2 * e->n, e->snaps + (size_t)s.best_slot[b] * 2 * e->n,
+                                     (size_t)2 * e->n * 4, hipMemcpyDeviceToHost));
+    }
+    return KMAP_OK;
+}
+
 int kmap_embed_get_losses(kmap_embed *e, float *losses, int64_t max_n, int64_t *n_out, void *stream) {
     KMAP_REQUIRE(e && n_out, "embed_get_losses: null");
     KMAP_CHECK_HIP(hipStreamSynchronize(as_stream(stream)));

@@ -381,6 +381,13 @@ class EmbedSession:
         check(_ffi.lib().kmap_embed_get_best(self._h, ptr(out), stream))
         return out
 
+    def best_list(self, stream=None):
+        """-> (snapshots [n_best, 2, N], losses [n_best]) in the best list's order"""
+        snaps = np.empty((self.n_best, 2, self.n), np.float32)
+        losses = np.empty(self.n_best, np.float32)
+        check(_ffi.lib().kmap_embed_get_best_list(self._h, ptr(snaps), ptr(losses), stream))
+        return snaps, losses
+
     def losses(self, max_n=1 << 16, stream=None):
         out = np.empty(max_n, np.float32)
         m = _ffi.i64(0)
@@ -425,8 +432,11 @@ def _run_loop(sess, n_max_iter, step_fn=None, debug=False, trace=None):
     t_loop = time.perf_counter()
     while info["iters"] < n_max_iter and not info["stopped"]:
         seg = min(_SEGMENT, n_max_iter - info["iters"])
-        if len(pool) - info["jitter_used"] < 2 * seg:
-            pool = np.concatenate([pool, np.random.normal(0, 0.01, _JITTER_CHUNK)])
+        if len(pool) - info["jitter_used"] < 2 * seg:       # a segment takes at most 2 normals per iteration (add_jitter)
+            extra = [np.random.normal(0, 0.01, _JITTER_CHUNK)]
+            while len(pool) + _JITTER_CHUNK * len(extra) - info["jitter_used"] < 2 * seg:
+                extra.append(np.random.normal(0, 0.01, _JITTER_CHUNK))
+            pool = np.concatenate([pool] + extra)
             sess.set_jitter(pool)
         if step_fn is None:
             sess.step(seg)

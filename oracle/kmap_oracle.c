@@ -13,6 +13,7 @@
  *
  * Build: see oracle/Makefile  (gcc -O2 -fopenmp -ffp-contract=off, no fast-math).
  */
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -361,4 +362,63 @@ void ko_gradient_rows(const float *T, const float *y, int64_t n, float *g) {
             g[kk * n + i] = s;
         }
     }
+}
+
+/* ---- one SEQ iteration of the embedding loop, fused: visualization.py:296-317 ----------------
+ * From the coordinates y (2 x n) and the probabilities p (n x n, f32): q per pair exactly as
+ * cal_ld_prob_mat (f32 1/(1 + (dx*dx + dy*dy)), diagonal 1, then the clip to [1e-3, 1 - 1e-3]
+ * with the bounds numpy converts from the Python doubles), T = (q/(1-q))*(p-q), the row sums of
+ * ko_gradient_rows (j ascending, no FMA; rows spread over threads, each row sequential), and
+ * the update y += (-(4 g)) * lr once every row is done.  *loss_out receives the loss of the
+ * coordinates BEFORE the update: 2 * sum_{i<j} CE as a float64 sum of the f32 terms of
+ * cross_entropy (the numpy oracle sums the same terms pairwise in f32; the loss only decides the
+ * best list and the stop rule).  No n x n scratch: q and T are recomputed per row.  Returns 0, or -1 (y untouched) when the
+ * O(n) scratch cannot be allocated. */
+int ko_embed_step_seq(const float *p, float *y, int64_t n, float lr, double *loss_out) {
+    const float qhi = (float)(1 - 1e-3), qlo = (float)1e-3, eps = (float)1e-10;
+    float *g = (float *)malloc((size_t)(n ? 2 * n : 1) * sizeof *g);
+    double *rl = (double *)malloc((size_t)(n ? n : 1) * sizeof *rl);
+    if (!g || !rl) {                    /* nothing touched: the caller raises */
+        free(g);
+        free(rl);
+        return -1;
+    }
+    const float *x0 = y, *x1 = y + n;
+#pragma omp parallel for schedule(dynamic, 16) if (n >= 512)
+    for (int64_t i = 0; i < n; ++i) {
+        const float *pr = p + i * n;
+        float xi = x0[i], yi = x1[i], s0 = 0.0f, s1 = 0.0f;
+        double l = 0.0;
+        for (int64_t j = 0; j < n; ++j) {
+            float dx = xi - x0[j], dy = yi - x1[j];
+            float q = 1.0f / (1.0f + (dx * dx + dy * dy));
+            if (j == i) q = 1.0f;
+            q = q < qhi ? q : qhi;      /* np.minimum / np.maximum (q is never NaN for finite y) */
+            q = q > qlo ? q : qlo;
+            if (j > i) {
+                float pv = pr[j], ce;
+                if (pv < eps) ce = -logf(1.0f - q);
+                else ce = (-pv) * logf(q) - (1.0f - pv) * logf(1.0f - q);
+                l += (double)ce;
+            }
+            if (j == i) continue;
+            float t = (q / (1.0f - q)) * (pr[j] - q);
+            float a = t * dx, b = t * dy;
+            s0 = s0 + a;
+            s1 = s1 + b;
+        }
+        g[i] = s0;
+        g[n + i] = s1;
+        rl[i] = l;
+    }
+    double loss = 0.0;
+    for (int64_t i = 0; i < n; ++i) loss += rl[i];
+    for (int64_t k = 0; k < 2 * n; ++k) {
+        float g4 = 4.0f * g[k];
+        y[k] = y[k] + (-g4) * lr;
+    }
+    *loss_out = loss * 2.0;
+    free(g);
+    free(rl);
+    return 0;
 }

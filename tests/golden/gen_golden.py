@@ -15,7 +15,8 @@ are stored (as .npz / text data files).
 Groups: ops (G2-G5 operator vectors), scan (G1,G6-G8 pipeline on tests/test.fa),
 embed (G9,G10 smoothing + umap traces), report (occurrence-file consumers and Hamming-ball
 extraction: position density, co-occurrence matrices, count matrices), occ20 (occurrence rows with the
-> 20-hit random subsample), earlystop (umap runs that end by the early-stop rule).
+> 20-hit random subsample), earlystop (umap runs that end by the early-stop rule), long (two umap runs at the default
+2500-iteration horizon, with the reference's own probabilities, checkpoints, best list and the RNG state it leaves).
 """
 import os
 import pickle
@@ -410,6 +411,71 @@ def gen_earlystop():
     save("umap_earlystop.npz", **out)
 
 
+LONG_CHECKPOINTS = (1, 255, 256, 257, 511, 512, 1024, 2048, 2499, 2500)
+
+
+def gen_long():
+    """umap runs of the reference at its default horizon (kmap() defaults: 2500 iterations, lr 0.01, 10 best, 20 neighbours) on two
+    sub-matrices of the N=300 matrix.  s15: 4047 jitter hits (the normal pool is refilled during the run), loss still falling at
+    the end.  n128: the loss oscillates, the returned snapshot comes from inside the run.  Stored: the reference's own hd_prob_mat
+    `p` (so later comparisons do not depend on the host's numpy exp), the init, every loss, the jitter hits per iteration, the
+    coordinates at a few checkpoints (checkpoint i = coordinates after i updates and jitters; checkpoint 0 = init; the snapshot
+    of loss index j is checkpoint j) and at every iteration of the final best list, that list, the returned array and one
+    np.random.randint(2**31) drawn right after kmap() returned."""
+    import bisect
+    z = np.load(HERE / "scan_testfa.npz", allow_pickle=False)
+    D = z["hamdist_mat_u8"].astype(np.int64)
+    k = int(z["hamdist_kmer_len"])
+    n_nb, n_best = 20, 10
+    out = {"kmer_len": np.array(k), "n_nb": np.array(n_nb)}
+    for tag, step, sub, seed in (("s15", 3, 96, 15), ("n128", 2, 128, 5)):
+        idx = np.arange(0, 300, step)[:sub]
+        Dm = D[np.ix_(idx, idx)]
+        losses, snaps, jit, probs = [], [], [], []
+        o_ce, o_jit = vz.cross_entropy_taichi, vz.add_jitter
+
+        def ce(hd, ldp, im):
+            if not probs:
+                probs.append(np.array(hd, copy=True))
+            v = o_ce(hd, ldp, im)
+            losses.append(v)
+            return v
+
+        def aj(ld_data, eps):
+            before = ld_data.copy()
+            r = o_jit(ld_data, eps)
+            jit.append(int(np.count_nonzero(before != r)))
+            snaps.append(r.copy())
+            return r
+
+        vz.cross_entropy_taichi, vz.add_jitter = ce, aj
+        try:
+            final = vz.kmap(Dm, k, debug=False, random_seed=seed)       # the reference's defaults otherwise
+        finally:
+            vz.cross_entropy_taichi, vz.add_jitter = o_ce, o_jit
+        draw = np.random.randint(2 ** 31)
+        nbm = np.argpartition(Dm, n_nb, axis=1)[:, :n_nb].astype(np.int32)
+        np.random.seed(seed)
+        init = np.random.randn(2, len(Dm)).astype("float32")
+        # the best list of visualization.py:304-308, replayed on the run's own losses (float64 keys, insort_right)
+        best = [(np.inf, -1)] * n_best
+        for j, v in enumerate(losses):
+            if v < best[-1][0]:
+                best = best[:-1]
+                best.insert(bisect.bisect_right([b[0] for b in best], float(v)), (float(v), j))
+        best_iters = np.array([b[1] for b in best], np.int64)
+        coords = [init] + snaps                                     # coords[i] = checkpoint i
+        assert np.array_equal(coords[best_iters[0]], final)
+        ck = np.array(sorted(set(LONG_CHECKPOINTS) | {int(b) for b in best_iters if b >= 0}), np.int64)
+        print(f"  long {tag}: N={sub} seed={seed}: {len(losses)} losses, {sum(jit)} jitter hits, best iterations {best_iters.tolist()}")
+        out.update({f"{tag}_D": Dm.astype(np.uint8), f"{tag}_nb": nbm, f"{tag}_seed": np.array(seed),
+                    f"{tag}_p": np.asarray(probs[0], np.float32), f"{tag}_init": init,
+                    f"{tag}_losses": np.array(losses, dtype=np.float32), f"{tag}_jitter_hits": np.array(jit, np.int32),
+                    f"{tag}_ckpt_iters": ck, f"{tag}_ckpt_coords": np.array([coords[i] for i in ck], np.float32),
+                    f"{tag}_best_iters": best_iters, f"{tag}_final": final, f"{tag}_next_randint": np.array(draw, np.int64)})
+    save("umap_long.npz", **out)
+
+
 def _synthetic_occurrence_file(path, rng, n_reads=400, n_motif=4):
     """An occurrence CSV in the reference's format with 4 motifs, multi-hit cells (up to 20 sorted locations), empty
     cells and varying read lengths -- input data for the consumers, written by this script (not by the reference)."""
@@ -629,8 +695,8 @@ def gen_occ20():
 
 
 if __name__ == "__main__":
-    groups = sys.argv[1:] or ["ops", "scan", "embed", "report", "occ20", "scan2", "earlystop"]
+    groups = sys.argv[1:] or ["ops", "scan", "embed", "report", "occ20", "scan2", "earlystop", "long"]
     for g in groups:
         print(f"[{g}]")
         {"ops": gen_ops, "scan": gen_scan, "embed": gen_embed, "report": gen_report, "occ20": gen_occ20, "scan2": gen_scan2,
-         "earlystop": gen_earlystop}[g]()
+         "earlystop": gen_earlystop, "long": gen_long}[g]()

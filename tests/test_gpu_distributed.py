@@ -222,6 +222,61 @@ def test_two_ranks_with_repeated_kmers_equal_single(tmp_path, monkeypatch):
     np.testing.assert_array_equal(best2, best)
 
 
+def _long_inputs():
+    """the n128 case of tests/golden/umap_long.npz as a k-mer sample: rows arange(0, 300, 2)[:128] of the expanded sample behind
+    scan_testfa.npz's N = 300 Hamming matrix, with the reference run's neighbour table and seed"""
+    z = np.load(ROOT / "tests" / "golden" / "scan_testfa.npz")
+    u = np.load(ROOT / "tests" / "golden" / "umap_long.npz")
+    idx = np.arange(0, 300, 2)[:128]
+    kh = np.repeat(z["samp_kh"], z["samp_cnts"])[idx]
+    lab = np.repeat(z["samp_label"], z["samp_cnts"])[idx]
+    return (kh, np.ones(len(idx), np.int64), lab, [str(c) for c in z["samp_conseqs"]], int(z["hamdist_kmer_len"]), u["n128_nb"],
+            int(u["n128_seed"]), u["n128_D"])
+
+
+def _long_worker(rank, world, port, out_dir):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), KMAP_DIST_EXCHANGE="rccl")
+    import torch
+    import torch.distributed as dist
+    from kmap_amd.distributed import kmap_from_kmers_distributed
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        kh, cnts, lab, conseqs, k, nb, seed, _ = _long_inputs()
+        tr = {}
+        best, _ = kmap_from_kmers_distributed(kh, cnts, lab, conseqs, k, n_max_iter=2500, random_seed=seed, mode=1,
+                                              neighbor_inds_mat=nb, trace=tr)
+        np.savez(Path(out_dir) / f"long_rank{rank}.npz", best=best, last=tr["last_coords"], losses=tr["losses"])
+    finally:
+        dist.destroy_process_group()
+
+
+def test_two_ranks_full_horizon_equals_single(tmp_path):
+    """Two SEQ row shards (64 + 64 rows) on one GPU for the default 2500 iterations on the n128 case of tests/golden/umap_long.npz:
+    the loss trace (each rank's loss partial travels as 48.48 fixed-point limbs through the all-reduce and is decoded on every
+    rank) is the single-GPU float64 reduction's f32 trace bit for bit, so the best list and the stop rule take the same decisions
+    over the whole run; the final coordinates, the returned array and its iteration are the same bit for bit."""
+    import torch.multiprocessing as mp
+    import kmap_amd.visualization as V
+    from oracle import oracle as O
+    from tests._long_horizon import replay_best_list
+    kh, cnts, lab, conseqs, k, nb, seed, D = _long_inputs()
+    # the sample is the fixture's matrix: the same Hamming distances, label overrides included
+    np.testing.assert_array_equal(O.hamdist_matrix_u8(kh, lab.astype(np.int32), k, [len(c) for c in conseqs]), D)
+    mp.spawn(_long_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    r0, r1 = np.load(tmp_path / "long_rank0.npz"), np.load(tmp_path / "long_rank1.npz")
+    np.testing.assert_array_equal(r0["losses"], r1["losses"])
+    np.testing.assert_array_equal(r0["best"], r1["best"])
+    tr = {}
+    best, _ = V.kmap_from_kmers(kh, cnts, lab, conseqs, k, n_max_iter=2500, random_seed=seed, mode=V.EMBED_SEQ, neighbor_inds_mat=nb,
+                                trace=tr)
+    assert len(tr["losses"]) == len(r0["losses"]) == 2500
+    np.testing.assert_array_equal(r0["losses"], tr["losses"])
+    np.testing.assert_array_equal(r0["last"], tr["last_coords"])
+    np.testing.assert_array_equal(r0["best"], best)
+    assert replay_best_list(r0["losses"])[0] == replay_best_list(tr["losses"])[0]
+
+
 def _count_worker(rank, world, port, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import pickle
