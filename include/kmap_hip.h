@@ -429,7 +429,8 @@ int kmap_embed_create(kmap_embed **e, int64_t n, int64_t row0, int64_t nrows, in
  * I = r, r + world, ... (cyclic: the upper-triangle work of a block shrinks with I).  Its probability rows are passed block
  * after block (local block b = rows [256 (r + world b), +256) of the matrix; kmap_embed_cyclic_blocks gives their number).
  * kmap_embed_forces then writes partial gradients for ALL points (rows and columns the rank touched) into grad_dev -- the
- * ranks' buffers are summed by the all-reduce (a true sum here, unlike the row-sharded sessions' concatenation). */
+ * ranks' buffers are summed by the all-reduce (a true sum here, unlike the row-sharded sessions' concatenation).
+ * Every rank must own a block: n <= (world - 1) * 256 is rejected (KMAP_E_INVAL). */
 int kmap_embed_create_cyclic(kmap_embed **e, int64_t n, int world, int rank, int n_best, float learning_rate);
 int64_t kmap_embed_cyclic_blocks(int64_t n, int world, int rank);
 int kmap_embed_destroy(kmap_embed *e);

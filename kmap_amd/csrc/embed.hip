@@ -415,6 +415,10 @@ int64_t kmap_embed_cyclic_blocks(int64_t n, int world, int rank) {
 
 int kmap_embed_create_cyclic(kmap_embed **out, int64_t n, int world, int rank, int n_best, float learning_rate) {
     KMAP_REQUIRE(world >= 1 && rank >= 0 && rank < world, "embed_create_cyclic: bad world / rank");
+    // every rank must own a row block: a rank without one would launch the tile kernel with a zero grid dimension and send a
+    // message that nothing writes
+    KMAP_REQUIRE(n > 0 && (n + SY_R - 1) / SY_R >= world, "embed_create_cyclic: n=%lld gives %lld row blocks of %d for %d ranks",
+                 (long long)n, (long long)((n + SY_R - 1) / SY_R), SY_R, world);
     return embed_create_impl(out, n, 0, n, n_best, learning_rate, KMAP_EMBED_FAST, world, rank);
 }
 

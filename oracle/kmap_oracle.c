@@ -422,3 +422,43 @@ int ko_embed_step_seq(const float *p, float *y, int64_t n, float lr, double *los
     free(rl);
     return 0;
 }
+
+/* ---- float64 checker of the FAST forces: visualization.py:131-145,162-176 + taichi_core.py:252-326 ----------------
+ * For sampled rows whose probabilities arrive as a slab (Pslab[r * n + j] = p(rows[r], j), f32), in float64 from the f32
+ * inputs: q = clip(1 / (1 + d2), 1e-3, 0.999), t = q / (1 - q) * (p - q) and
+ *   g[c * n_rows + r]   = sum_{j != i} t (y_i - y_j)_c                        the raw gradient (kmap_embed_forces' convention)
+ *   mag[c * n_rows + r] = sum_{j != i} |q / (1 - q)| (|p| + q) |y_i - y_j|_c  no cancellation: the scale of the f32 error
+ *   loss[r]             = sum_{j > i} ce(p, q), the reference's cross-entropy with its eps = 1e-10 branches.
+ * The f32 kernels' per-pair error in p - q is a few ulps of q, not of |p - q|: hence |p| + q in mag. */
+void ko_embed_forces_rows_f64(const float *Pslab, const int64_t *rows, int64_t n_rows, const float *y, int64_t n, double *g,
+                              double *mag, double *loss) {
+    const double qlo = 1e-3, qhi = 1.0 - 1e-3, eps = 1e-10;
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t i = rows[r];
+        const double xi = y[i], yi = y[n + i];
+        const float *p = Pslab + r * n;
+        double gx = 0.0, gy = 0.0, mx = 0.0, my = 0.0, l = 0.0;
+        for (int64_t j = 0; j < n; ++j) {
+            if (j == i) continue;
+            const double dx = xi - (double)y[j], dy = yi - (double)y[n + j];
+            double q = 1.0 / (1.0 + (dx * dx + dy * dy));
+            q = q < qlo ? qlo : (q > qhi ? qhi : q);
+            const double pv = p[j], w = q / (1.0 - q), t = w * (pv - q), a = w * (fabs(pv) + q);
+            gx += t * dx;
+            gy += t * dy;
+            mx += a * fabs(dx);
+            my += a * fabs(dy);
+            if (j > i) {
+                if (pv < eps) l += -log(1.0 - q);
+                else if (pv > 1.0 - eps) l += -log(q);
+                else l += -pv * log(q) - (1.0 - pv) * log(1.0 - q);
+            }
+        }
+        g[r] = gx;
+        g[n_rows + r] = gy;
+        mag[r] = mx;
+        mag[n_rows + r] = my;
+        loss[r] = l;
+    }
+}

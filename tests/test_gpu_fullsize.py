@@ -327,6 +327,44 @@ def _assert_seq_rows_equal_oracle(g, sums_d, lds, lut, coords, rows):
     assert np.abs(want).max() > 0
 
 
+def _fast_rows_vs_f64(n, sums_d, lds, lut, coords, g, kappa, pairs=(), what=""):
+    """the FAST gradient per element against the float64 oracle on >= 256 sampled rows (edges of row blocks and column tiles,
+    the SEQ form edges, `pairs`' rows) -- tests/_fast_check.py; with `pairs`: each pair's term stands >= 100x above the bound"""
+    from tests import _fast_check as F
+    rows = np.union1d(F.check_rows(n, rows_extra=[r for p in pairs for r in p], rng_rows=96), _seq_form_rows(n))
+    assert len(rows) >= 256
+    P = np.empty((len(rows), n), np.float32)
+    for t, r in enumerate(rows):
+        P[t] = lut[sums_d.to_numpy(np.uint16, (lds,), offset=int(r) * lds * 2)[:n]]
+    g64, M, _ = F.reference(lambda rr: P, rows, coords)
+    r = F.assert_forces_close(g[:, rows], g64, M, kappa, rows, what)
+    power = None
+    if pairs:
+        pos = {int(x): t for t, x in enumerate(rows)}
+        p = [P[pos[i], j] for i, j in pairs]
+        power = F.assert_pairs_visible(pairs, F.pair_terms(coords, pairs, p), rows, M, kappa)
+    print(f"FASTCHECK {what} n={n} err/(uM)={r:.3f}" + (f" power={power:.0f}" if power is not None else ""))
+
+
+def _fast_planted(n, sums_d, lds, lut, coords):
+    """one FAST evaluation with pairs planted through the coordinates (tests/_fast_check.py structural positions, moved out of
+    the cloud) -> (pairs, planted coordinates, gradient)"""
+    from kmap_amd import _ffi, visualization as V
+    from tests import _fast_check as F
+    pairs = F.structural_pairs(n)
+    yp = F.plant_far(coords, pairs)
+    sess = V.EmbedSession(n, 10, 0.01, V.EMBED_FAST)
+    _ffi.check(_ffi.lib().kmap_embed_set_prob_lut(sess._h, sums_d.ptr, lds, _ffi.ptr(lut), len(lut)))
+    sess.set_coords(yp)
+    g_d = _ffi.DeviceBuffer(2 * n * 4)
+    sess.forces(g_d.ptr)
+    _ffi.sync()
+    g = g_d.to_numpy(np.float32, (2, n))
+    sess.close()
+    g_d.free()
+    return pairs, yp, g
+
+
 def test_c3_embedding_force_evaluation_full_size():
     """N = 50 000 with the hand-over's label structure: the symmetric FAST kernel (the opt-in mode) against the SEQ kernel (the default: the
     reference's summation order) on one force evaluation -- loss to 2e-6, gradient to 2e-5 of its scale -- and 20 FAST
@@ -392,6 +430,11 @@ def test_c3_embedding_force_evaluation_full_size():
             losses = sess.losses()
             assert len(losses) == 20 and np.all(np.isfinite(losses)) and losses[-1] < losses[0]
         sess.close()
+    # the symmetric FAST kernel per element against float64: these coordinates, and pairs planted through the coordinates
+    from tests import _fast_check as F
+    _fast_rows_vs_f64(n, sums_d, lds, lut, coords, outs["fast"][0], F.kappa("sym", n), what="sym c3 natural")
+    pairs, yp, gp = _fast_planted(n, sums_d, lds, lut, coords)
+    _fast_rows_vs_f64(n, sums_d, lds, lut, yp, gp, F.kappa("sym", n), pairs, what="sym c3 planted")
     sums_d.free()
     (gs, ls), (gf, lf) = outs["seq"], outs["fast"]
     assert abs(lf - ls) <= 2e-6 * abs(ls)
@@ -662,6 +705,12 @@ def test_c4_embedding_force_evaluation_full_size():
     l3 = loss_from_limbs(msum[2 * n:])
     assert abs(l3 - lf) <= 1e-9 * abs(lf)                                       # the same pairs, f64 partials in another grouping
     np.testing.assert_allclose(msum[:2 * n].reshape(2, n), gf, rtol=0, atol=3e-6 * np.abs(gf).max())
+    # per element against float64: the one-GPU symmetric kernel, the summed cyclic shards, and pairs planted through the coordinates
+    from tests import _fast_check as F
+    _fast_rows_vs_f64(n, sums_d, lds, lut, coords, gf, F.kappa("sym", n), what="sym c4 natural")
+    _fast_rows_vs_f64(n, sums_d, lds, lut, coords, msum[:2 * n].reshape(2, n), F.kappa("cyclic", n, 3), what="cyclic c4 natural world=3")
+    pairs, yp, gp = _fast_planted(n, sums_d, lds, lut, coords)
+    _fast_rows_vs_f64(n, sums_d, lds, lut, yp, gp, F.kappa("sym", n), pairs, what="sym c4 planted")
     for b in (sums_d, nb_d, kh_d, lab_d):
         b.free()
 
