@@ -176,8 +176,19 @@ __global__ __launch_bounds__(KMAP_WAVE *WAVES_PER_BLOCK) void hamdist_matrix_ker
 //    pack = 2.75 ops per byte for k <= 8, 4.75 for k <= 16.
 // Tile = one 4-KiB column block x R rows spaced 8 apart (all its chunks share one residue); requires ld % 4096 == 0 and
 // ld / 4096 odd (kmap_amd.hamdist.pitch_for provides it).
+// Packed tail: when the last column block holds at most 2048 valid columns (tw = 1 or 2 of its four 1024-column wave quarters),
+// a normal tile there keeps one or two waves busy and lets the others leave at once, yet holds one of the CU's four slots for
+// a whole residency (N = 50 000: 848 of 4096 columns, 1/13 of all tiles for 1.7 % of the bytes).  That block is tiled on its
+// own: a tail workgroup covers m = 4 / tw row sets of its chunk column, wave w taking row set w / tw and column quarter
+// w % tw, so all four waves store and there are m times fewer tail workgroups.  A row set is R rows spaced 8 apart with the
+// workgroup's residue, exactly a normal tile's rows, so (a) and (b) hold as they are and (c) is the same LDS reservation.
+// The grid is one-dimensional, so no workgroup is launched for a (column block, row group) nobody owns: first the
+// 8 * cbm * groups normal tiles in row-group order (column blocks fastest), then the 8 * ceil(groups / m) tail tiles; both
+// counts are multiples of 8, so (id & 7) is a block's XCD.
 constexpr int T_TPB = 256;
+constexpr int T_WAVES = T_TPB / KMAP_WAVE;
 constexpr int T_LDS_THROTTLE = 40 * 1024;   // dynamic LDS reserved per block: four resident blocks per CU (rule (c) above)
+constexpr uint32_t T_MAX_BLOCKS = 0xFFFFFFFFu / T_TPB;   // a one-dimensional launch holds fewer than 2^32 threads
 
 template <typename H>
 __global__ void build_codes_kernel(const H *__restrict__ kh, int64_t n, int k, H mask, int onehot, uint32_t *__restrict__ c0,
@@ -204,26 +215,46 @@ template <int CW, int R>
 __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__restrict__ c0, const uint32_t *__restrict__ c1,
                                                              const uint8_t *__restrict__ gid, ByteTab gshift, int k, int64_t n,
                                                              int64_t row0, int64_t nrows, uint8_t *__restrict__ out, int64_t ld,
-                                                             int cb, int inv, int shift) {
-    // grid = (8 * cb, groups): the linear workgroup id is y * 8cb + x, so (blockIdx.x & 7) is the XCD the block lands on
-    const int x = (int)(blockIdx.x & 7);
-    const int c = (int)(blockIdx.x >> 3);
-    const int64_t g = blockIdx.y;
+                                                             int cbm, uint32_t cbm_magic, uint32_t n_main, int tw, int inv,
+                                                             int shift) {
+    // grid = n_main normal tiles + the packed tail tiles; (id & 7) is the XCD the block lands on in both parts
+    const uint32_t id = blockIdx.x;
+    const int x = (int)(id & 7);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const bool tail = id >= n_main;                                   // block-uniform
+    int c, q;                     // column block, 1024-column quarter of it
+    int64_t g;                    // row set: rows g * 8 R + rho + 8 j
+    if (!tail) {
+        // y = id / w8 without a division: cbm_magic = floor(2^32 / w8) gives the quotient or one less
+        const uint32_t w8 = 8u * (uint32_t)cbm;
+        uint32_t y = __umulhi(id, cbm_magic), rem = id - y * w8;
+        if (rem >= w8) ++y, rem -= w8;
+        c = (int)(rem >> 3);
+        g = y;
+        q = wave;
+    } else {                      // tw is 1 or 2 here
+        c = cbm;
+        g = (int64_t)((id - n_main) >> 3) * (T_WAVES >> (tw - 1)) + (wave >> (tw - 1));
+        q = wave & (tw - 1);
+    }
     const int rho = ((((x - c - shift) % 8 + 8) % 8) * inv) & 7;      // (ld/4096 * row + c + shift) % 8 == x
-    // the tile's R row codes / group ids: one vector load per wave up front (lane j holds row j), v_readlane per row.
+    const int64_t rbase = g * (8 * R) + rho;
+    // the wave's row codes / group ids: one vector load per wave up front (lane j holds row j), v_readlane per row.
     // Nothing is loaded inside the row loop, so no s_waitcnt vmcnt ever waits on the stores already issued.  Loaded BEFORE
     // lanes past the last column leave: v_readlane must find lanes 0..R-1 written even in a wave that keeps only lane 0.
     const int lane = threadIdx.x & (KMAP_WAVE - 1);
-    const int64_t my_rl = g * (8 * R) + rho + 8 * (lane < R ? lane : 0);
+    const int64_t my_rl = rbase + 8 * (lane < R ? lane : 0);
     const bool rv = lane < R && my_rl < nrows;
     const uint32_t ra0 = rv ? c0[row0 + my_rl] : 0u;
     const uint32_t ra1 = (CW == 2 && rv) ? c1[row0 + my_rl] : 0u;
     const uint32_t rgid = rv ? (uint32_t)gid[row0 + my_rl] : 0u;
 
-    const int64_t col0 = (int64_t)c * 4096 + (int64_t)threadIdx.x * COLS_PER_LANE;
-    // only whole waves leave (wave-uniform); lanes past the last column stay and are predicated off, so that every lane the
-    // v_readlane's below read from is live
-    if ((int64_t)c * 4096 + (int64_t)(threadIdx.x & ~(KMAP_WAVE - 1)) * COLS_PER_LANE >= n) return;
+    const int64_t wcol0 = (int64_t)c * 4096 + (int64_t)q * COLS_PER_WAVE;
+    const int64_t col0 = wcol0 + (int64_t)lane * COLS_PER_LANE;
+    // only whole waves leave (wave-uniform): past the last column (normal tiles of a partial last block) or past the last row
+    // (the last tail workgroup's unused row sets); lanes past the last column stay and are predicated off, so that every lane
+    // the v_readlane's below read from is live
+    if (wcol0 >= n || rbase >= nrows) return;
     const bool full = col0 + COLS_PER_LANE <= n;
 
     uint32_t nb0[COLS_PER_LANE], nb1[CW == 2 ? COLS_PER_LANE : 1], gcol[COLS_PER_LANE / 4];
@@ -264,7 +295,7 @@ __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__r
 
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-        const int64_t rloc = g * (8 * R) + rho + 8 * j;          // row inside this call's output (wave-uniform)
+        const int64_t rloc = rbase + 8 * j;                      // row inside this call's output (wave-uniform)
         if (rloc >= nrows) break;
         const uint32_t a0 = rl(ra0, j);
         const uint32_t a1 = (CW == 2) ? rl(ra1, j) : 0u;
@@ -376,11 +407,20 @@ int launch_tile(const uint32_t *c0, const uint32_t *c1, const uint8_t *gid, cons
     for (int t = 1; t < 8; t += 2)
         if (((cpr * t) & 7) == 1) inv = t;
     const int shift = (int)(((uintptr_t)out >> 12) & 7);
+    // the last column block: tw of its four wave quarters hold columns; with tw <= 2 it gets packed tail tiles (n >= 4096, so
+    // a block with fewer than 4096 columns is never the only one)
+    const int tw = (int)((n - (int64_t)(cb - 1) * 4096 + COLS_PER_WAVE - 1) / COLS_PER_WAVE);
+    const bool pack = tw <= 2;
+    const int cbm = pack ? cb - 1 : cb;                      // column blocks served by normal tiles
     const int64_t groups = (nrows + 8 * R - 1) / (8 * R);
-    KMAP_REQUIRE(groups <= 65535, "hamdist_matrix: nrows too large for one launch (%lld)", (long long)nrows);
-    const dim3 blocks((unsigned)(8 * cb), (unsigned)groups);
+    const int m = pack ? T_WAVES / tw : 1;                   // row sets per tail workgroup
+    const int64_t n_main = 8 * cbm * groups, n_tail = pack ? 8 * ((groups + m - 1) / m) : 0;
+    KMAP_REQUIRE(n_main + n_tail <= (int64_t)T_MAX_BLOCKS, "hamdist_matrix: %lld rows x %lld columns are too many tiles for one launch",
+                 (long long)nrows, (long long)n);
     KMAP_TRY(kmap_allow_lds((const void *)hamdist_tile_kernel<CW, R>, 160 * 1024));
-    hamdist_tile_kernel<CW, R><<<blocks, T_TPB, T_LDS_THROTTLE, st>>>(c0, c1, gid, gshift, k, n, row0, nrows, out, ld, cb, inv, shift);
+    hamdist_tile_kernel<CW, R><<<dim3((unsigned)(n_main + n_tail)), T_TPB, T_LDS_THROTTLE, st>>>(
+        c0, c1, gid, gshift, k, n, row0, nrows, out, ld, cbm, (uint32_t)((1ull << 32) / (8u * (unsigned)cbm)), (uint32_t)n_main, pack ? tw : 0,
+        inv, shift);
     KMAP_CHECK_HIP(hipGetLastError());
     return KMAP_OK;
 }
