@@ -408,6 +408,35 @@ int kmap_gather_rows_u8_dev(const uint8_t *D_dev, int64_t ldd, int64_t n, const 
 /* generic float form in the reference's summation order (any distance matrix) */
 int kmap_knn_smooth_f32(const float *D, const int32_t *nb, int64_t n, int n_nb, float *S_out);
 
+/* ---- projection of new k-mers onto an existing map (project_kmers; csrc/project.hip, DESIGN.md "Projection") ------------------
+ * M query k-mers against N reference k-mers whose 2-D coordinates are fixed.  All three are asynchronous on `stream`; m = 0
+ * (nrows = 0) is a no-op that returns KMAP_OK; every other bad argument returns KMAP_E_INVAL with a message, never a fault.
+ *
+ * Selection: q_dev[m] in/out (on return the oriented hashes), ref_dev[n], 1 <= k <= 15 (u32) / 31 (u64), 1 <= n_nb <= 64, n_nb <= n
+ * < 2^31.  With revcom != 0 a query is replaced by its reverse complement iff that strand's smallest plain Hamming distance (all k
+ * bases, no label rule) to the references is STRICTLY smaller than the forward strand's; flipped_dev[m] (uint8) says so.
+ * nb_dev: int32 [m, n_nb], the reference indices with the smallest (distance, index) pairs in that order -- the tie rule of
+ * the device selection above; nb_dist_dev: uint8 [m, n_nb], their distances. */
+int kmap_project_knn_u32_dev(uint32_t *q_dev, int64_t m, const uint32_t *ref_dev, int64_t n, int k, int revcom, int n_nb,
+                             int32_t *nb_dev, uint8_t *nb_dist_dev, uint8_t *flipped_dev, void *stream);
+int kmap_project_knn_u64_dev(uint64_t *q_dev, int64_t m, const uint64_t *ref_dev, int64_t n, int k, int revcom, int n_nb,
+                             int32_t *nb_dev, uint8_t *nb_dist_dev, uint8_t *flipped_dev, void *stream);
+/* Query sums and probabilities of queries [row0, row0 + nrows) (nrows <= 65535 per call): Q[r][j] = sum over the query's n_nb
+ * neighbours a of sums[row(a)][j] (uint16 rows of pitch lds elements, n payload columns; row(a) = rowmap_dev[a] when the rows
+ * are stored de-duplicated -- src_rows of them --, a itself when rowmap_dev is NULL and src_rows == n), p_dev[r][j] =
+ * lut_dev[Q[r][j]] (float32, pitch ldp elements, local row r = query row0 + r).  qsum_dev (may be NULL): Q itself as uint32 with
+ * the pitch of p.  lut_dev: lut_len floats in device memory; an index behind the table reads its last entry. */
+int kmap_project_prob_dev(const int32_t *nb_dev, int64_t m, int n_nb, const uint16_t *sums_dev, int64_t lds, const int32_t *rowmap_dev,
+                          int64_t src_rows, int64_t n, const float *lut_dev, int64_t lut_len, int64_t row0, int64_t nrows, float *p_dev,
+                          int64_t ldp, uint32_t *qsum_dev, void *stream);
+/* Start and descent of queries [row0, row0 + nrows) from their p rows (as written by kmap_project_prob_dev for the same range):
+ * y = sum_a p[a] ref_xy[:, a] / sum_a p[a] over the query's neighbours a, then n_iter times y -= learning_rate * 4 * sum_j
+ * q/(1-q) (p[j] - q) (y - ref_xy[:, j]) with q = clip(1 / (1 + |y - ref_xy[:, j]|^2), 1e-3, 1 - 1e-3) over all n references, float32,
+ * the whole loop in one launch.  ref_xy_dev: float32 [2, n]; xy_dev: float32 [2, m], entries [row0, row0 + nrows) of both planes
+ * are written. */
+int kmap_project_descend_dev(const float *p_dev, int64_t ldp, const int32_t *nb_dev, int64_t m, int n_nb, const float *ref_xy_dev,
+                             int64_t n, int64_t row0, int64_t nrows, int n_iter, float learning_rate, float *xy_dev, void *stream);
+
 /* ---- embedding operators (drop-in L3): visualization.py:131-176,235-256, taichi_core.py:252-326 */
 int kmap_ld_prob_mat_f32(const float *ld_2xn, int64_t n, float *q_out_nxn);          /* incl. clip */
 int kmap_cross_entropy_f32(const float *p_nxn, const float *q_nxn, int64_t n, float *loss_out);

@@ -134,6 +134,10 @@ _SIGS = {
     "kmap_rows_fresh_u8_dev": (i32, [vp, i64, i64, i64, i64, vp, vp]),
     "kmap_gather_rows_u8_dev": (i32, [vp, i64, i64, vp, i64, vp, i64, vp]),
     "kmap_knn_smooth_f32": (i32, [vp, vp, i64, i32, vp]),
+    "kmap_project_knn_u32_dev": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+    "kmap_project_knn_u64_dev": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+    "kmap_project_prob_dev": (i32, [vp, i64, i32, vp, i64, vp, i64, i64, vp, i64, i64, i64, vp, i64, vp, vp]),
+    "kmap_project_descend_dev": (i32, [vp, i64, vp, i64, i32, vp, i64, i64, i64, i32, f32, vp, vp]),
     "kmap_ld_prob_mat_f32": (i32, [vp, i64, vp]),
     "kmap_cross_entropy_f32": (i32, [vp, vp, i64, vp]),
     "kmap_gradient_loss_f32": (i32, [vp, vp, vp, i64, vp]),

@@ -3,7 +3,8 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+figures), and `project_kmers`, which the reference does not have: new k-mers placed on the map `visualize_kmers` wrote, without moving
+its points (projection.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -87,3 +88,14 @@ def extract_motif_locations(bed_file, conseq_file="./final_conseq.txt", motif_oc
 def check_motif_co_occurence(input_fasta_file, motif1, motif2, max_ham_dist1, max_ham_dist2, output_dir, revcom_mode=True):
     from .locations import check_motif_co_occurence as run
     run(input_fasta_file, motif1, motif2, max_ham_dist1, max_ham_dist2, output_dir, revcom_mode)
+
+
+@cli.command(name="project_kmers")
+@click.option("--res_dir", type=str, required=True, help="Result directory of scan_motif / visualize_kmers (holds low_dim_data.tsv)")
+@click.option("--kmer_file", type=str, required=True, help="Input file, one k-mer per line, of the sampled k-mers' length")
+@click.option("--output_file", type=str, default=None, required=False,
+              help="output file name, including the suffix (default: projected_kmers.tsv in res_dir)")
+@click.option("--n_iter", type=int, default=100, required=False, help="gradient steps per projected k-mer")
+def project_kmers(res_dir, kmer_file, output_file=None, n_iter=100):
+    from .projection import _project_kmers
+    _project_kmers(res_dir, kmer_file, output_file, n_iter)

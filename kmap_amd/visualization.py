@@ -520,6 +520,45 @@ def kmap(hamdist_mat: np.ndarray, kmer_len: int, n_neighbour=20, n_max_iter=2500
     return out
 
 
+def sums_rows_from_kmers(kh, lab, kmer_len, lens, n_neighbour, neighbor_inds_mat=None, natural_diag=False, trace=None,
+                         matrix_fallback=True):
+    """Expanded hashes and labels -> (sums_d, lds): the integer neighbour-sum rows (uint16 on the device) of the smoothing step.
+    The neighbours are `neighbor_inds_mat` or the selection of `knn_mode(n)` on the device Hamming matrix; the sums come from the
+    profile kernel (`knn_sums_kmers_dev`) and, where it does not cover the request, from the matrix (zero diagonal) --
+    matrix_fallback=False raises ValueError naming the limit instead (project_kmers needs the natural diagonal)."""
+    n = len(kh)
+    ldd = pitch_for(n)
+    need_matrix = matrix_fallback or neighbor_inds_mat is None
+    with _stage("hamdist_matrix"):
+        kh_d, lab_d = _ffi.DeviceBuffer.from_numpy(kh), _ffi.DeviceBuffer.from_numpy(lab)
+        D_d = None
+        if need_matrix:
+            D_d = _ffi.DeviceBuffer(n * ldd)
+            hamdist_matrix_dev(kh_d.ptr, lab_d.ptr, n, kmer_len, lens, D_d.ptr, ldd)
+    try:
+        with _stage("knn_select"):
+            if neighbor_inds_mat is None and knn_mode(n) == "device":
+                neighbor_inds_mat = knn_select_dev(D_d.ptr, ldd, n, n_neighbour)
+            elif neighbor_inds_mat is None:
+                # drop-in neighbour choice: numpy argpartition on int64 rows, streamed back in row blocks
+                neighbor_inds_mat = knn_select_numpy(D_d.ptr, ldd, n, n_neighbour)
+        if trace is not None and not isinstance(neighbor_inds_mat, _ffi.DeviceBuffer):
+            trace["nb"] = np.asarray(neighbor_inds_mat)            # the host-chosen neighbours (numpy mode / injected)
+        with _stage("knn_sums"):
+            res = knn_sums_kmers_dev(kh_d.ptr, lab_d.ptr, n, kmer_len, lens, neighbor_inds_mat, n_neighbour, natural_diag=natural_diag)
+            if res is None and not matrix_fallback:
+                raise ValueError("neighbour sums with the natural diagonal need the profile kernel (k <= 16, at most 4 consensuses "
+                                 f"shorter than k, n_neighbour^2 k <= 65535): {_ffi.last_error()}")
+            sums_d, lds = res if res is not None else knn_sums_dev(D_d.ptr, ldd, neighbor_inds_mat, n, n_neighbour)
+    finally:
+        if isinstance(neighbor_inds_mat, _ffi.DeviceBuffer):
+            neighbor_inds_mat.free()
+        for b in (D_d, kh_d, lab_d):
+            if b is not None:
+                b.free()
+    return sums_d, lds
+
+
 def kmap_from_kmers(samp_kh, samp_cnts, samp_label, conseq_list, kmer_len, n_neighbour=20, n_max_iter=2500,
                     learning_rate=0.01, n_best_result=10, random_seed=None, debug=False, mode=None,
                     neighbor_inds_mat=None, trace=None):
@@ -530,26 +569,8 @@ def kmap_from_kmers(samp_kh, samp_cnts, samp_label, conseq_list, kmer_len, n_nei
     lab = np.repeat(np.asarray(samp_label), samp_cnts).astype(np.int32)
     n = len(kh)
     lens = [len(c) for c in conseq_list]
-    ldd = pitch_for(n)
-    with _stage("hamdist_matrix"):
-        kh_d, lab_d = _ffi.DeviceBuffer.from_numpy(kh), _ffi.DeviceBuffer.from_numpy(lab)
-        D_d = _ffi.DeviceBuffer(n * ldd)
-        hamdist_matrix_dev(kh_d.ptr, lab_d.ptr, n, kmer_len, lens, D_d.ptr, ldd)
-    with _stage("knn_select"):
-        if neighbor_inds_mat is None and knn_mode(n) == "device":
-            neighbor_inds_mat = knn_select_dev(D_d.ptr, ldd, n, n_neighbour)
-        elif neighbor_inds_mat is None:
-            # drop-in neighbour choice: numpy argpartition on int64 rows, streamed back in row blocks
-            neighbor_inds_mat = knn_select_numpy(D_d.ptr, ldd, n, n_neighbour)
-    if trace is not None and not isinstance(neighbor_inds_mat, _ffi.DeviceBuffer):
-        trace["nb"] = np.asarray(neighbor_inds_mat)            # the host-chosen neighbours (numpy mode / injected)
-    with _stage("knn_sums"):
-        res = knn_sums_kmers_dev(kh_d.ptr, lab_d.ptr, n, kmer_len, lens, neighbor_inds_mat, n_neighbour, natural_diag=mode == EMBED_SEQ)
-        sums_d, lds = res if res is not None else knn_sums_dev(D_d.ptr, ldd, neighbor_inds_mat, n, n_neighbour)
-    if isinstance(neighbor_inds_mat, _ffi.DeviceBuffer):
-        neighbor_inds_mat.free()
-    for b in (D_d, kh_d, lab_d):
-        b.free()
+    sums_d, lds = sums_rows_from_kmers(kh, lab, kmer_len, lens, n_neighbour, neighbor_inds_mat, natural_diag=mode == EMBED_SEQ,
+                                       trace=trace)
     lut = hd_prob_lut(kmer_len, n_neighbour, n_neighbour * n_neighbour * kmer_len)
     ld_data, placeholders = _init_draws(n, n_best_result, random_seed)
     rowmap_d, stored = None, n
