@@ -128,9 +128,8 @@ int kmap_counts_fetch(kmap_counts *c, void *uniq_out, void *cnt_out);
 /* the same copy on a caller-chosen stream through pinned staging buffers (conversion on host threads): lets a background host
  * thread drain a finished table (multi-GB at k >= 14) while the default stream keeps counting into another handle */
 int kmap_counts_fetch_stream(kmap_counts *c, void *uniq_out, void *cnt_out, void *stream);
-/* elements [first, first + count) of one array of the table in the reference's dtype: which = 0 unique hashes, 1 counts */
-int kmap_counts_fetch_range(kmap_counts *c, int which, int64_t first, int64_t count, void *out, void *stream);
-/* the same range written into an open file instead (pwrite at file_offset; the descriptor's own position is untouched): pinned
+/* elements [first, first + count) of one array of the table in the reference's dtype (which = 0 unique hashes, 1 counts), written
+ * into an open file (pwrite at file_offset; the descriptor's own position is untouched): pinned
  * staging, the next chunk crossing PCIe while the current one is written, counts widened on the device -- the k{k}.pkl writers of
  * multi-GB tables (reference motif_discovery.py:642-645 pickles [k, uniq, cnt]) */
 int kmap_counts_write_range(kmap_counts *c, int which, int64_t first, int64_t count, int fd, int64_t file_offset, void *stream);
@@ -214,8 +213,6 @@ int kmap_pack_planes_dev(const uint32_t *codes_dev, int64_t n, uint32_t *planes_
 typedef struct kmap_scan kmap_scan;
 int kmap_scan_create(kmap_scan **s);
 int kmap_scan_destroy(kmap_scan *s);
-int kmap_scan_run_dev(kmap_scan *s, const uint8_t *seq_dev, int64_t n, const int64_t *borders_dev, int64_t n_seq,
-                      int k, uint64_t cons, int radius, int revcom, int64_t *total_hits, void *stream);
 /* Optional: the caller declares that read s of `borders_dev` is [s * stride, s * stride + read_len) (fixed-length reads, as the reference's
  * FASTA encoder lays them out: motif_discovery.py:1422-1477 walks such reads one by one).  Verified on the device; *accepted = 1 when
  * true.  Runs of this handle on the same border array then derive the borders from s instead of loading them (16 B per read).  The

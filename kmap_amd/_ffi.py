@@ -65,7 +65,6 @@ _SIGS = {
     "kmap_counts_fetch": (i32, [vp, vp, vp]),
     "kmap_counts_fetch_stream": (i32, [vp, vp, vp, vp]),
     "kmap_counts_table_dev": (i32, [vp, P(vp), P(vp), P(i64)]),
-    "kmap_counts_fetch_range": (i32, [vp, i32, i64, i64, vp, vp]),
     "kmap_counts_write_range": (i32, [vp, i32, i64, i64, i32, i64, vp]),
     "kmap_counts_total": (i32, [vp, P(i64)]),
     "kmap_hamball_extract": (i32, [vp, vp, i64, i32, u64, i32, i32, vp, vp, P(i64), vp]),
@@ -102,7 +101,6 @@ _SIGS = {
     "kmap_scan_create": (i32, [P(vp)]),
     "kmap_scan_declare_uniform": (i32, [vp, vp, i64, i64, i64, P(i32), vp]),
     "kmap_scan_destroy": (i32, [vp]),
-    "kmap_scan_run_dev": (i32, [vp, vp, i64, vp, i64, i32, u64, i32, i32, P(i64), vp]),
     "kmap_scan_fetch": (i32, [vp, vp, vp, vp]),
     "kmap_scan_fetch_stream": (i32, [vp, vp, vp, vp]),
     "kmap_scan_fetch_stream_u8": (i32, [vp, vp, vp, vp]),

@@ -879,29 +879,16 @@ __global__ __launch_bounds__(256) void scan_reorder_kernel(const int32_t *__rest
     }
 }
 
-unsigned grid_of(int64_t n, int64_t per) {
-    const int64_t g = (n + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
-int pc2_host(uint32_t x) { return __builtin_popcount((x | (x >> 1)) & 0x55555555u); }
-uint32_t rc_host(uint32_t c, int k) {
-    const uint32_t m = low_mask<uint32_t>(k);
-    uint32_t com = m - c, r = com & 3u;
-    for (int i = 0; i < k - 1; ++i) { r <<= 2; com >>= 2; r += com & 3u; }
-    return r;
-}
-
 template <int K>
 void launch_hits(const uint32_t *planes, const uint16_t *inval, int64_t n, int64_t n_alloc, const HitTab &tab, uint16_t *hit16, bool words,
                  hipStream_t st) {
     const char *v = getenv("KMAP_SCAN_PLANES");                          // "plain": the formulation without the index mode (tests compare the two)
     const bool idx = !(v && !strcmp(v, "plain"));
     const int64_t n_words = (n + 31) / 32;
-    if (idx && words) hits_planes_idx_kernel<K, true><<<grid_of(n_words, 2 * BS_TPB), BS_TPB, 0, st>>>(planes, inval, n, n_alloc, tab, hit16);
-    else if (idx) hits_planes_idx_kernel<K, false><<<grid_of(n_words, 2 * BS_TPB), BS_TPB, 0, st>>>(planes, inval, n, n_alloc, tab, hit16);
-    else if (words) hits_planes_kernel<K, true><<<grid_of(n_words, BS_TPB), BS_TPB, 0, st>>>(planes, inval, n, n_alloc, tab, hit16);
-    else hits_planes_kernel<K, false><<<grid_of(n_words, BS_TPB), BS_TPB, 0, st>>>(planes, inval, n, n_alloc, tab, hit16);
+    if (idx && words) hits_planes_idx_kernel<K, true><<<grid_for(n_words, 2 * BS_TPB), BS_TPB, 0, st>>>(planes, inval, n, n_alloc, tab, hit16);
+    else if (idx) hits_planes_idx_kernel<K, false><<<grid_for(n_words, 2 * BS_TPB), BS_TPB, 0, st>>>(planes, inval, n, n_alloc, tab, hit16);
+    else if (words) hits_planes_kernel<K, true><<<grid_for(n_words, BS_TPB), BS_TPB, 0, st>>>(planes, inval, n, n_alloc, tab, hit16);
+    else hits_planes_kernel<K, false><<<grid_for(n_words, BS_TPB), BS_TPB, 0, st>>>(planes, inval, n, n_alloc, tab, hit16);
 }
 
 }  // namespace
@@ -918,15 +905,10 @@ int kmap_bitslice_hits(const uint32_t *planes, const uint16_t *inval, int64_t n,
     for (int c = 0; c < n_cons; ++c) {
         HitCons &e = tab.c[c];
         e.fwd = (uint32_t)cons[c] & km;
-        e.rc = rc_host(e.fwd, k);
+        e.rc = (uint32_t)host_revcom(e.fwd, k, k < 16);
         e.two = revcom_pairs ? 1u : 0u;
         e.radius = radius[c];
-        int d_inv = pc2_host((km ^ e.fwd) & km);
-        if (e.two) {
-            const int d2 = pc2_host((km ^ e.rc) & km);
-            d_inv = d2 < d_inv ? d2 : d_inv;
-        }
-        e.inv_hit = d_inv <= e.radius ? ~0u : 0u;
+        e.inv_hit = host_invalid_dist(e.fwd, e.rc, k, revcom_pairs) <= e.radius ? ~0u : 0u;
     }
     const int64_t n_alloc = kmap_packed_groups(n);
     switch (k) {
@@ -986,12 +968,8 @@ static HrCtx make_ctx(const uint32_t *hit32, const uint32_t *codes, const uint16
     c.hit32 = hit32; c.codes = codes; c.inval = inval; c.n = n; c.n_alloc = kmap_packed_groups(n); c.k = k; c.revcom = revcom; c.radius = radius;
     c.km = low_mask<uint32_t>(k);
     c.cons = (uint32_t)cons & c.km;
-    c.rcc = rc_host(c.cons, k);
-    c.d_inv = pc2_host((c.km ^ c.cons) & c.km);
-    if (revcom) {
-        const int d2 = pc2_host((c.km ^ c.rcc) & c.km);
-        c.d_inv = d2 < c.d_inv ? d2 : c.d_inv;
-    }
+    c.rcc = (uint32_t)host_revcom(c.cons, k, k < 16);
+    c.d_inv = host_invalid_dist(c.cons, c.rcc, k, revcom);
     return c;
 }
 
@@ -1000,7 +978,7 @@ int kmap_bitslice_scan_reads(bool write, const uint32_t *hit32, const uint32_t *
                              hipStream_t st) {
     HrCtx c = make_ctx(hit32, codes, inval, n, k, cons, revcom, radius);
     scan_geometry(s, borders, n_seq, c);
-    const unsigned grid = grid_of(n_seq, HR_TPB);
+    const unsigned grid = grid_for(n_seq, HR_TPB);
     const bool chk = c.d_inv <= radius;            // only then can a hit be a window that touches an invalid position
     // s->offs doubles as [block offsets uint64 (n_blocks + 1) | block sums uint32 (n_blocks)]: n_seq + 1 uint64 are allocated
     uint32_t *bsums = reinterpret_cast<uint32_t *>(s->offs + (size_t)grid + 1);
@@ -1078,7 +1056,7 @@ int kmap_pack_planes_dev(const uint32_t *codes_dev, int64_t n, uint32_t *planes_
     const int64_t ng = kmap_packed_groups(n);
     KMAP_REQUIRE(codes_dev && planes_dev, "pack_planes: null pointer");
     KMAP_REQUIRE((((uintptr_t)codes_dev | (uintptr_t)planes_dev) & 7u) == 0u, "pack_planes: codes / planes must be 8-byte aligned (whole arrays, not offsets into them)");
-    planes_kernel<<<grid_of(ng / 2, BS_TPB), BS_TPB, 0, as_stream(stream)>>>(codes_dev, ng / 2, planes_dev);   // ng is even
+    planes_kernel<<<grid_for(ng / 2, BS_TPB), BS_TPB, 0, as_stream(stream)>>>(codes_dev, ng / 2, planes_dev);   // ng is even
     KMAP_CHECK_HIP(hipGetLastError());
     return KMAP_OK;
 }

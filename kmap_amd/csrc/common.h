@@ -96,3 +96,35 @@ __device__ __forceinline__ uint64_t revcom_hash(uint64_t h, int k) {
     r = ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);
     return (r >> (64 - 2 * k)) & low_mask<uint64_t>(k);
 }
+
+// ---- host helpers -----------------------------------------------------------------------------
+// blocks of per_block elements that cover n, at least one
+static inline unsigned grid_for(int64_t n, int64_t per_block) {
+    int64_t g = (n + per_block - 1) / per_block;
+    return (unsigned)(g < 1 ? 1 : g);
+}
+// reverse complement of a k-mer hash on the host: same arithmetic as the device helper above (`narrow`: the hashes are uint32,
+// k < 16, and the complement wraps in u32 like the reference's when h is not below 4^k)
+static inline uint64_t host_revcom(uint64_t h, int k, int narrow) {
+    if (narrow) {
+        uint32_t mask = (uint32_t)((1ull << (2 * k)) - 1), com = mask - (uint32_t)h, r = com & 3u;
+        for (int i = 0; i < k - 1; ++i) { r <<= 2; com >>= 2; r += com & 3u; }
+        return r;
+    }
+    uint64_t mask = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1), com = mask - h, r = com & 3u;
+    for (int i = 0; i < k - 1; ++i) { r <<= 2; com >>= 2; r += com & 3u; }
+    return r;
+}
+// number of non-zero 2-bit groups of x (popc2 above, on the host)
+static inline int host_popc2(uint64_t x) { return __builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull); }
+// distance of an invalid window (all ones in its 2k bits, compared like any value) from cons -- with `revcom`, from the nearer of
+// cons and its reverse complement rcc
+static inline int host_invalid_dist(uint64_t cons, uint64_t rcc, int k, int revcom) {
+    const uint64_t m = low_mask<uint64_t>(k);
+    int d = host_popc2((m ^ cons) & m);
+    if (revcom) {
+        const int d2 = host_popc2((m ^ rcc) & m);
+        d = d2 < d ? d2 : d;
+    }
+    return d;
+}

@@ -18,7 +18,9 @@ struct kmap_counts {
 };
 // does the shared table still hold THIS handle's last histogram? (KMAP_E_STATE + message otherwise)
 int kmap_counts_bins_check(const kmap_counts *c, const char *who);
-
+// room for `entries` table entries in the handle's uniq / cnt arrays (kept when they already hold as many; their contents are not).
+// On failure the handle is left empty -- no arrays, cap = 0, n_uniq = 0, k = 0: "nothing counted yet" -- and KMAP_E_NOMEM returned
+int kmap_counts_reserve_table(kmap_counts *c, size_t entries);
 
 // k >= 17: sort + run-length encode + revcom merge (counts_sort.hip)
 int kmap_counts_sort_path(kmap_counts *c, const uint64_t *hash_dev, int64_t n, int k, int merge, int64_t *n_uniq,

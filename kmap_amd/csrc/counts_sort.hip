@@ -238,14 +238,7 @@ int kmap_counts_sort_path(kmap_counts *c, const uint64_t *hash_dev, int64_t n, i
     uint64_t total = 0;
     TRYH(hipMemcpyAsync(&total, off + m, 8, hipMemcpyDeviceToHost, st));
     TRYH(hipStreamSynchronize(st));
-    if (c->cap < total || !c->uniq) {
-        if (c->uniq) (void)hipFree(c->uniq);
-        if (c->cnt) (void)hipFree(c->cnt);
-        c->uniq = nullptr; c->cnt = nullptr; c->cap = 0;
-        TRYH(hipMalloc(&c->uniq, (size_t)(total ? total : 1) * 8));
-        TRYH(hipMalloc((void **)&c->cnt, (size_t)(total ? total : 1) * 4));
-        c->cap = total ? total : 1;
-    }
+    { int r = kmap_counts_reserve_table(c, (size_t)total); if (r != KMAP_OK) { cleanup(); return r; } }
     scatter_kernel<<<grid, BLK, 0, st>>>(flag, off, mkey, mcnt, m, (uint64_t *)c->uniq, c->cnt);
     TRYH(hipGetLastError());
     TRYH(hipStreamSynchronize(st));

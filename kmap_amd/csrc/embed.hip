@@ -389,13 +389,6 @@ __global__ __launch_bounds__(BLK) void sym_apply_kernel(LoopState *__restrict__ 
 
 }  // namespace
 
-namespace {
-void drop_graph(kmap_embed *e) {   // kernel arguments changed: the captured iterations are stale
-    if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
-    e->gexec = nullptr;
-}
-}  // namespace
-
 extern "C" {
 
 // ---- session ---------------------------------------------------------------------------------
@@ -488,8 +481,6 @@ static int embed_create_impl(kmap_embed **out, int64_t n, int64_t row0, int64_t 
 
 int kmap_embed_destroy(kmap_embed *e) {
     if (!e) return KMAP_OK;
-    if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
-    if (e->gstream) (void)hipStreamDestroy(e->gstream);
     void *ptrs[] = {e->Y, e->G, e->snaps, e->loss_log, e->loss_part, e->loss_sum, e->states, e->lut_dev, e->normals,
                     e->rowpart, e->colpart, e->n_normals_dev};
     for (void *p : ptrs)
@@ -515,7 +506,6 @@ int kmap_embed_set_prob_f32(kmap_embed *e, const float *p_rows_dev, int64_t ld) 
     }
     e->src = ProbSrc{p_rows_dev, nullptr, nullptr, ld, 0, nullptr, e->nrows};
     e->have_prob = true;
-    drop_graph(e);
     return KMAP_OK;
 }
 
@@ -525,7 +515,6 @@ int kmap_embed_set_prob_lut(kmap_embed *e, const uint16_t *sums_rows_dev, int64_
     KMAP_CHECK_HIP(hipMemcpy(e->lut_dev, lut, (size_t)lut_len * 4, hipMemcpyHostToDevice));
     e->src = ProbSrc{nullptr, sums_rows_dev, e->lut_dev, ld, lut_len, nullptr, e->nrows};
     e->have_prob = true;
-    drop_graph(e);
     return KMAP_OK;
 }
 
@@ -534,7 +523,6 @@ int kmap_embed_set_row_map(kmap_embed *e, const int32_t *rowmap_dev, int64_t src
     if (!rowmap_dev) {
         e->src.rowmap = nullptr;
         e->src.src_rows = e->nrows;
-        drop_graph(e);
         return KMAP_OK;
     }
     KMAP_REQUIRE(e->mode == KMAP_EMBED_SEQ && !e->sym, "embed_set_row_map: SEQ sessions only (the FAST kernels read one stored row per session row)");
@@ -546,7 +534,6 @@ int kmap_embed_set_row_map(kmap_embed *e, const int32_t *rowmap_dev, int64_t src
     KMAP_REQUIRE(ok, "embed_set_row_map: the map must start at 0, end at src_rows - 1 and step by 0 or 1");
     e->src.rowmap = rowmap_dev;
     e->src.src_rows = src_rows;
-    drop_graph(e);
     return KMAP_OK;
 }
 
@@ -564,7 +551,7 @@ int kmap_embed_set_coords(kmap_embed *e, const float *coords_2xn, const float *p
 int kmap_embed_set_jitter(kmap_embed *e, const double *normals, int n_normals) {
     KMAP_REQUIRE(e && n_normals >= 0 && (n_normals == 0 || normals), "embed_set_jitter: bad arguments");
     KMAP_CHECK_HIP(hipDeviceSynchronize());
-    if (n_normals > e->normals_cap) {           // grow geometrically: the pointer (a kernel argument) rarely changes
+    if (n_normals > e->normals_cap) {           // grow geometrically: refills rarely reallocate
         int cap = e->normals_cap ? e->normals_cap : 8192;
         while (cap < n_normals) cap *= 2;
         if (e->normals) KMAP_CHECK_HIP(hipFree(e->normals));
@@ -572,7 +559,6 @@ int kmap_embed_set_jitter(kmap_embed *e, const double *normals, int n_normals) {
         e->normals_cap = 0;
         KMAP_CHECK_HIP(hipMalloc((void **)&e->normals, (size_t)cap * 8));
         e->normals_cap = cap;
-        drop_graph(e);
     }
     if (n_normals) KMAP_CHECK_HIP(hipMemcpy(e->normals, normals, (size_t)n_normals * 8, hipMemcpyHostToDevice));
     KMAP_CHECK_HIP(hipMemcpy(e->n_normals_dev, &n_normals, 4, hipMemcpyHostToDevice));
@@ -607,36 +593,6 @@ int launch_iteration(kmap_embed *e, hipStream_t st) {
     KMAP_CHECK_HIP(hipGetLastError());
     e->cur ^= 1;
     return KMAP_OK;
-}
-
-// capture two iterations (parities cur, cur ^ 1) into a graph; any failure switches graph replay off for the session
-bool ensure_graph(kmap_embed *e) {
-    if (e->graph_failed) return false;
-    if (e->gexec) return true;
-    // opt-in (KMAP_EMBED_GRAPH=1): measured on ROCm 7.2 / MI355X, replaying the captured pair of iterations is SLOWER than
-    // launching the same 2-3 kernels directly (N = 50 k FAST 0.958 vs 0.882 ms / iteration, N = 5 k SEQ 0.175 vs 0.163, FAST 0.047 vs
-    // 0.041): the launches are already queued ahead of the GPU, and the graph adds per-node dispatch cost
-    static const bool on = [] { const char *v = getenv("KMAP_EMBED_GRAPH"); return v && v[0] == '1'; }();
-    if (!on) { e->graph_failed = true; return false; }
-    if (!e->gstream && hipStreamCreateWithFlags(&e->gstream, hipStreamNonBlocking) != hipSuccess) { e->graph_failed = true; return false; }
-    hipGraph_t graph = nullptr;
-    const int cur0 = e->cur;
-    bool ok = hipStreamBeginCapture(e->gstream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    if (ok) {
-        ok = launch_iteration(e, e->gstream) == KMAP_OK && launch_iteration(e, e->gstream) == KMAP_OK;
-        ok = (hipStreamEndCapture(e->gstream, &graph) == hipSuccess) && ok && graph;
-    }
-    e->cur = cur0;                                   // captured, not executed
-    if (ok) ok = hipGraphInstantiate(&e->gexec, graph, nullptr, nullptr, 0) == hipSuccess;
-    if (graph) (void)hipGraphDestroy(graph);
-    if (!ok) {
-        (void)hipGetLastError();
-        e->gexec = nullptr;
-        e->graph_failed = true;
-        return false;
-    }
-    e->graph_cur = cur0;
-    return true;
 }
 }  // namespace
 
@@ -732,22 +688,7 @@ int kmap_embed_step(kmap_embed *e, int n_iter, void *stream) {
     KMAP_REQUIRE(e && e->row0 == 0 && e->nrows == e->n && e->world == 1, "embed_step: single-GPU convenience needs all rows local");
     KMAP_REQUIRE(e->have_prob && e->have_coords, "embed_step: probabilities/coordinates not set");
     hipStream_t st = as_stream(stream);
-    int it = 0;
-    if (n_iter >= 4 && ensure_graph(e)) {
-        if (e->cur != e->graph_cur && it < n_iter) {   // realign the parity the graph was captured at
-            KMAP_TRY(launch_iteration(e, st));
-            ++it;
-        }
-        for (; it + 2 <= n_iter; it += 2) {
-            if (hipGraphLaunch(e->gexec, st) != hipSuccess) {   // e.g. a stream the runtime cannot launch graphs into
-                (void)hipGetLastError();
-                drop_graph(e);
-                e->graph_failed = true;
-                break;
-            }
-        }
-    }
-    for (; it < n_iter; ++it) KMAP_TRY(launch_iteration(e, st));
+    for (int it = 0; it < n_iter; ++it) KMAP_TRY(launch_iteration(e, st));
     return KMAP_OK;
 }
 

@@ -92,15 +92,10 @@ struct kmap_embed {
     // work per block shrinks with I); its probability rows are stored block after block (local block b = I / world)
     int world = 1, rank = 0;
     int64_t n_lblocks = 0;
-    // jitter normals: fixed-capacity device buffer + device-resident count, so that the kernel arguments of an iteration never
-    // change between launches (a captured hipGraph stays valid when the host refills the pool)
+    // jitter normals: device buffer + device-resident count. The count is a device word because every apply kernel takes it as a
+    // pointer argument: the host refills the pool without changing what an iteration is launched with
     int *n_normals_dev = nullptr;
     int normals_cap = 0;
-    // two iterations (both parities of the double-buffered loop record) captured as one hipGraph and replayed by kmap_embed_step
-    hipGraphExec_t gexec = nullptr;
-    hipStream_t gstream = nullptr;
-    int graph_cur = 0;
-    bool graph_failed = false;
 };
 
 // ---- launchers (one per force-kernel family); loss partials go to e->loss_part --------------------------------------------------

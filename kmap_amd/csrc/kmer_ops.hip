@@ -3,17 +3,13 @@
 // Each replaces one numpy-in/numpy-out operator of the reference (cited at the entry points).
 // All of these are HBM-streaming integer kernels: 1 B (sequence) or 4/8 B (hash) per element.
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 
 namespace {
 
 constexpr int BLK = 256;
-
-static inline unsigned grid_for(int64_t n, int per_block) {
-    int64_t g = (n + per_block - 1) / per_block;
-    return (unsigned)(g < 1 ? 1 : g);
-}
 
 // ---- hash at every position (taichi_core.py:3-61) ------------------------------------------------
 // A thread owns POS consecutive positions and rolls the 2-bit window across them: it reads
@@ -273,13 +269,11 @@ int dedupe_launch(H *hash_dev, int64_t n, const int64_t *borders_dev, int64_t n_
     int rc = KMAP_OK;
     if (n_long > 0) {
         // host-side table layout: needs the long reads' lengths
-        int64_t *ids_h = (int64_t *)malloc((size_t)n_long * 8);
-        int64_t *off_h = (int64_t *)malloc(((size_t)n_long + 1) * 8);
-        int64_t *bh = (int64_t *)malloc((size_t)n_long * 16);
-        KMAP_CHECK_HIP(hipMemcpy(ids_h, long_ids, (size_t)n_long * 8, hipMemcpyDeviceToHost));
+        std::vector<int64_t> ids_h((size_t)n_long), off_h((size_t)n_long + 1), bh((size_t)n_long * 2);
+        KMAP_CHECK_HIP(hipMemcpy(ids_h.data(), long_ids, (size_t)n_long * 8, hipMemcpyDeviceToHost));
         // atomics give an arbitrary order; any order is fine (reads are independent)
         for (unsigned long long i = 0; i < n_long; ++i)
-            KMAP_CHECK_HIP(hipMemcpy(bh + 2 * i, borders_dev + 2 * ids_h[i], 16, hipMemcpyDeviceToHost));
+            KMAP_CHECK_HIP(hipMemcpy(bh.data() + 2 * i, borders_dev + 2 * ids_h[i], 16, hipMemcpyDeviceToHost));
         off_h[0] = 0;
         for (unsigned long long i = 0; i < n_long; ++i) {
             int64_t L = bh[2 * i + 1] - bh[2 * i];
@@ -293,7 +287,7 @@ int dedupe_launch(H *hash_dev, int64_t n, const int64_t *borders_dev, int64_t n_
         hipError_t e = hipMalloc((void **)&tab, tot * 16);
         if (e == hipSuccess) e = hipMalloc((void **)&off_d, ((size_t)n_long + 1) * 8);
         if (e == hipSuccess) e = hipMemsetAsync(tab, 0xFF, tot * 16, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(off_d, off_h, ((size_t)n_long + 1) * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(off_d, off_h.data(), ((size_t)n_long + 1) * 8, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) {
             dedupe_long_kernel<H><<<(unsigned)n_long, BLK, 0, st>>>(hash_dev, borders_dev, long_ids, off_d, tab,
                                                                     tab + tot, n);
@@ -306,9 +300,6 @@ int dedupe_launch(H *hash_dev, int64_t n, const int64_t *borders_dev, int64_t n_
         }
         if (tab) (void)hipFree(tab);
         if (off_d) (void)hipFree(off_d);
-        free(ids_h);
-        free(off_h);
-        free(bh);
     }
     return rc;
 }

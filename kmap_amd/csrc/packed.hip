@@ -10,7 +10,6 @@
 //
 // Kernels: pack / unpack, hash materialisation, histogram (LDS-privatised passes or global atomics) straight from the
 // packed stream, Hamming-ball mask (flag + coverage), and the per-read occurrence scan.
-#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -1075,11 +1074,6 @@ __global__ __launch_bounds__(FL_TPB) void scan_reads_kernel(const uint64_t *__re
     }
 }
 
-static inline unsigned grid_for(int64_t n, int64_t per) {
-    int64_t g = (n + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
 }  // namespace
 
 
@@ -1156,6 +1150,21 @@ int dedupe_skip_bits(const uint32_t *codes_dev, const uint16_t *inval_dev, int64
     *skip_out = skip;
     return KMAP_OK;
 }
+
+// the hash array of the packed reads (uint32 for k < 16, else uint64; the stream's KMAP_SLOT_HASH scratch), de-duplicated per read
+// on request: the way to the counts for reads longer than the LDS set of dedupe_skip_bits allows, and for k > 16
+int hash_and_dedupe(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, const int64_t *borders_dev, int64_t n_seq, int k,
+                    int dedupe_per_read, void *stream, void **hash_out) {
+    void *hash = nullptr;
+    KMAP_TRY(kmap_scratch(&hash, (size_t)(n ? n : 1) * (k < 16 ? 4 : 8), as_stream(stream), KMAP_SLOT_HASH));
+    KMAP_TRY(kmap_hash_kmers_packed_dev(codes_dev, inval_dev, n, k, hash, stream));
+    if (dedupe_per_read) {
+        if (k < 16) KMAP_TRY(kmap_dedupe_per_read_u32_dev((uint32_t *)hash, n, borders_dev, n_seq, stream));
+        else KMAP_TRY(kmap_dedupe_per_read_u64_dev((uint64_t *)hash, n, borders_dev, n_seq, stream));
+    }
+    *hash_out = hash;
+    return KMAP_OK;
+}
 }  // namespace
 
 // fills c->bins (zeroed first) with the k-mer histogram of the packed reads; k <= 16
@@ -1173,10 +1182,7 @@ int kmap_counts_hist_packed_dev(kmap_counts *c, const uint32_t *codes_dev, const
     if (dedupe_per_read && !skip) {
         // reads longer than the LDS set allows: per-read dedupe on a materialised hash array (any length)
         void *hash = nullptr;
-        KMAP_TRY(kmap_scratch(&hash, (size_t)(n ? n : 1) * (k < 16 ? 4 : 8), st, KMAP_SLOT_HASH));
-        KMAP_TRY(kmap_hash_kmers_packed_dev(codes_dev, inval_dev, n, k, hash, stream));
-        if (k < 16) KMAP_TRY(kmap_dedupe_per_read_u32_dev((uint32_t *)hash, n, borders_dev, n_seq, stream));
-        else KMAP_TRY(kmap_dedupe_per_read_u64_dev((uint64_t *)hash, n, borders_dev, n_seq, stream));
+        KMAP_TRY(hash_and_dedupe(codes_dev, inval_dev, n, borders_dev, n_seq, k, 1, stream, &hash));
         return kmap_counts_hist_hashes(c, hash, n, k, st);
     }
     if (kmap_counts_part_applies(k, n)) {
@@ -1187,18 +1193,14 @@ int kmap_counts_hist_packed_dev(kmap_counts *c, const uint32_t *codes_dev, const
     KMAP_TRY(kmap_counts_prepare_bins(c, k, st));
     if (n > 0) {
         const size_t n_bins = (size_t)1 << (2 * k);
-        const size_t passes = (n_bins + HP_BINS - 1) / HP_BINS;
-        static const bool wide_counters = [] { const char *v = getenv("KMAP_HIST16"); return v && v[0] == '0'; }();   // A/B switch: 32-bit LDS counters
-        if (n_bins >= (size_t)HP16_BINS && n_bins / HP16_BINS <= 16 && n >= (1 << 16) && !wide_counters) {
+        if (n_bins >= (size_t)HP16_BINS && n_bins / HP16_BINS <= 16 && n >= (1 << 16)) {
             // k = 8, 9: 16-bit LDS counters, 65 536 bins per pass
             KMAP_TRY(kmap_allow_lds((const void *)hist_packed16_kernel, (HP16_BINS / 2 + 64) * 4));
             for (size_t p = 0; p < n_bins / HP16_BINS; ++p)
                 hist_packed16_kernel<<<256, HP_TPB, (HP16_BINS / 2 + 64) * 4, st>>>(codes_dev, inval_dev, n, k, (uint32_t)(p * HP16_BINS), c->bins, skip);
-        } else if (passes <= 32 && n >= (1 << 16)) {   // k <= 10: 32 passes x 0.375 B/position still beat scattered device atomics
+        } else if (n_bins <= (size_t)HP_BINS && n >= (1 << 16)) {   // k <= 7: the whole table in one block's 32-bit LDS counters
             KMAP_TRY(kmap_allow_lds((const void *)hist_packed_kernel<false, true>, (HP_BINS + 64) * 4));
-            for (size_t p = 0; p < passes; ++p)
-                hist_packed_kernel<false, true><<<256, HP_TPB, (HP_BINS + 64) * 4, st>>>(codes_dev, inval_dev, n, k,
-                                                                                  (uint64_t)p * HP_BINS, c->bins, skip);
+            hist_packed_kernel<false, true><<<256, HP_TPB, (HP_BINS + 64) * 4, st>>>(codes_dev, inval_dev, n, k, 0, c->bins, skip);
         } else {
             int64_t g = ((n + 15) / 16 + BLK - 1) / BLK;
             if (g > 256 * 16) g = 256 * 16;
@@ -1231,13 +1233,9 @@ int kmap_counts_run_packed_dev(kmap_counts *c, const uint32_t *codes_dev, const 
     KMAP_REQUIRE(n >= 0 && codes_dev && inval_dev, "counts_run_packed: bad input");
     hipStream_t st = as_stream(stream);
     if (k > 16) {   // sort path on a materialised hash array
+        KMAP_REQUIRE(!dedupe_per_read || n_seq == 0 || borders_dev, "counts_run_packed: dedupe needs borders");
         void *hash = nullptr;
-        KMAP_TRY(kmap_scratch(&hash, (size_t)(n ? n : 1) * 8, st, KMAP_SLOT_HASH));
-        KMAP_TRY(kmap_hash_kmers_packed_dev(codes_dev, inval_dev, n, k, hash, stream));
-        if (dedupe_per_read) {
-            KMAP_REQUIRE(n_seq == 0 || borders_dev, "counts_run_packed: dedupe needs borders");
-            KMAP_TRY(kmap_dedupe_per_read_u64_dev((uint64_t *)hash, n, borders_dev, n_seq, stream));
-        }
+        KMAP_TRY(hash_and_dedupe(codes_dev, inval_dev, n, borders_dev, n_seq, k, dedupe_per_read, stream, &hash));
         return kmap_counts_run_hashes_dev(c, hash, n, k, merge_revcom, n_uniq, stream);
     }
     KMAP_TRY(kmap_counts_hist_packed_dev(c, codes_dev, inval_dev, n, borders_dev, n_seq, k, dedupe_per_read, stream));
@@ -1386,10 +1384,8 @@ int kmap_scan_run_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint
     KMAP_REQUIRE(k > 16 || planes_dev, "scan_run_packed: k <= 16 needs the bit planes (kmap_pack_planes_dev)");
     hipStream_t st = as_stream(stream);
     KMAP_TRY(kmap_scan_reserve(s, n_seq));
-    const uint64_t m = low_mask<uint64_t>(k);
-    const uint64_t c = cons & m;
-    uint64_t com = m - c, rcc = com & 3u;
-    for (int i = 0; i < k - 1; ++i) { rcc <<= 2; com >>= 2; rcc += com & 3u; }
+    const uint64_t c = cons & low_mask<uint64_t>(k);
+    const uint64_t rcc = host_revcom(c, k, k < 16);
     if (bitslice_on(k)) {
         // hit bit per window (bit-sliced, 0.125 B per position written), then the per-read passes evaluate the few hits exactly
         const int64_t ng = (n + 15) >> 4;
@@ -1417,13 +1413,7 @@ int kmap_scan_run_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint
         if (ng) {
             scan_nibble_kernel<<<grid_for(ng, BLK), BLK, 0, st>>>(codes_dev, inval_dev, n, k, c, rcc, radius, revcom, nib, wmin);
         }
-        // distance of an invalid window (all ones, compared like any value)
-        auto pc2 = [](uint64_t x) { return __builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull); };
-        d_inv = pc2((m ^ c) & m);
-        if (revcom) {
-            const int d2 = pc2((m ^ rcc) & m);
-            d_inv = d2 < d_inv ? d2 : d_inv;
-        }
+        d_inv = host_invalid_dist(c, rcc, k, revcom);
         scan_reads_kernel<false><<<fgrid, FL_TPB, 0, st>>>(nib, n, borders_dev, n_seq, k, d_inv, radius, s->hits, s->mind, nullptr, nullptr, wmin);
     } else {
         scan_packed_kernel<false><<<grid, KMAP_WAVE * SC_WAVES, 0, st>>>(codes_dev, inval_dev, n, borders_dev, n_seq, k, c, rcc,

@@ -1,99 +1,11 @@
-// scan.hip -- per-read motif occurrence scan ("Hamming-ball scan over reads", BASELINE config 5).
-// Replaces get_motif_occurence (reference motif_discovery.py:1422-1477), which per read and per
-// consensus launches one hash kernel + two Hamming kernels from Python.  Here: one wave per read,
-// hash windows rolled from the uint8 array (1 B per position), min(fwd, revcom) distance, wave-min of
-// the hits, ballot-ordered compaction of the positions at the read's minimum distance.
-//
-// Roofline: HBM-bound, 1 B per array position + sparse hit output.
+// scan.hip -- the handle of the per-read motif occurrence scan ("Hamming-ball scan over reads", BASELINE config 5; replaces
+// get_motif_occurence, reference motif_discovery.py:1422-1477): its result lists (reserve), their summary and the ways out of
+// the device (fetch).  The scan itself runs on the packed reads: kmap_scan_run_packed_dev (packed.hip, bitslice.hip).
 #include <algorithm>
 
 #include "common.h"
-#include "scan_util.h"
 
 namespace {
-
-constexpr int SC_WAVES = 4;
-
-// number of candidate positions = len(hash_arr[0 : L-k+1]) with Python slice semantics (negative stop wraps)
-__device__ __forceinline__ int64_t slice_stop(int64_t L, int k) {
-    int64_t stop = L - k + 1;
-    if (stop < 0) {
-        stop += L;
-        if (stop < 0) stop = 0;
-    }
-    return stop > L ? L : stop;
-}
-
-// min(fwd, rc) Hamming distance of the k-mer starting at read[p] (invalid window = all ones, compared as is)
-__device__ __forceinline__ int window_dist(const uint8_t *__restrict__ read, int64_t L, int64_t p, int k, uint64_t m,
-                                           uint64_t cons, uint64_t rcc, int revcom) {
-    uint64_t h = 0;
-    bool bad = (p + k > L);
-    for (int i = 0; i < k; ++i) {
-        const uint32_t b = (p + i < L) ? read[p + i] : 255u;
-        bad |= (b == 255u);
-        h = (h << 2) + b;
-    }
-    h = bad ? m : (h & m);
-    int d = popc2((h ^ cons) & m);
-    if (revcom) {
-        const int d2 = popc2((h ^ rcc) & m);
-        d = d2 < d ? d2 : d;
-    }
-    return d;
-}
-
-template <bool WRITE>
-__global__ __launch_bounds__(KMAP_WAVE *SC_WAVES) void scan_kernel(const uint8_t *__restrict__ seq, int64_t n,
-                                                                    const int64_t *__restrict__ borders, int64_t n_seq,
-                                                                    int k, uint64_t cons, uint64_t rcc, int radius,
-                                                                    int revcom, int32_t *__restrict__ hits,
-                                                                    int8_t *__restrict__ min_dist,
-                                                                    const uint64_t *__restrict__ offs,
-                                                                    int32_t *__restrict__ pos_out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);
-    if (s >= n_seq) return;
-    int64_t st = borders[2 * s], en = borders[2 * s + 1];
-    if (st < 0) st = 0;
-    if (en > n) en = n;
-    const int64_t L = en > st ? en - st : 0;
-    const uint8_t *read = seq + st;
-    const int64_t stop = slice_stop(L, k);
-    const uint64_t m = low_mask<uint64_t>(k);
-    int best;
-    if (!WRITE) {
-        best = 1 << 30;
-        for (int64_t p = lane; p < stop; p += 64) {
-            const int d = window_dist(read, L, p, k, m, cons, rcc, revcom);
-            if (d <= radius && d < best) best = d;
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const int v = __shfl_xor(best, o);
-            best = v < best ? v : best;
-        }
-    } else {
-        best = min_dist[s];
-        if (best < 0) return;
-    }
-    int count = 0;
-    uint64_t base = WRITE ? offs[s] : 0;
-    if (best <= radius) {
-        for (int64_t p0 = 0; p0 < stop; p0 += 64) {
-            const int64_t p = p0 + lane;
-            const bool hit = (p < stop) && (window_dist(read, L, p, k, m, cons, rcc, revcom) == best);
-            const unsigned long long mask = __ballot(hit);
-            if (WRITE && hit) pos_out[base + __popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)p;
-            const int c = __popcll(mask);
-            count += c;
-            base += c;
-        }
-    }
-    if (!WRITE && lane == 0) {
-        hits[s] = count;
-        min_dist[s] = (int8_t)((best <= radius) ? best : -1);
-    }
-}
 
 __global__ __launch_bounds__(256) void scan_summary_kernel(const int32_t *__restrict__ hits, int64_t n_seq,
                                                            unsigned long long *__restrict__ stat) {
@@ -176,40 +88,6 @@ int kmap_scan_destroy(kmap_scan *s) {
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete s;
-    return KMAP_OK;
-}
-
-int kmap_scan_run_dev(kmap_scan *s, const uint8_t *seq_dev, int64_t n, const int64_t *borders_dev, int64_t n_seq, int k,
-                      uint64_t cons, int radius, int revcom, int64_t *total_hits, void *stream) {
-    KMAP_REQUIRE(s, "scan_run: null handle");
-    KMAP_REQUIRE(k > 0 && k < 32, "scan_run: k=%d out of range", k);
-    KMAP_REQUIRE(n >= 0 && n_seq >= 0 && radius >= 0, "scan_run: negative size");
-    s->n_seq = n_seq;
-    s->total = 0;
-    if (total_hits) *total_hits = 0;
-    if (n_seq == 0) return KMAP_OK;
-    KMAP_REQUIRE(seq_dev && borders_dev, "scan_run: null pointer");
-    hipStream_t st = as_stream(stream);
-    KMAP_TRY(kmap_scan_reserve(s, n_seq));
-    const uint64_t m = low_mask<uint64_t>(k);
-    const uint64_t c = cons & m;
-    // reverse complement on the host (same arithmetic as revcom_hash; u32 wrap for k < 16 is moot: c < 4^k)
-    uint64_t com = m - c, rcc = com & 3u;
-    for (int i = 0; i < k - 1; ++i) { rcc <<= 2; com >>= 2; rcc += com & 3u; }
-    const unsigned grid = (unsigned)((n_seq + SC_WAVES - 1) / SC_WAVES);
-    scan_kernel<false><<<grid, KMAP_WAVE * SC_WAVES, 0, st>>>(seq_dev, n, borders_dev, n_seq, k, c, rcc, radius, revcom,
-                                                              s->hits, s->mind, nullptr, nullptr);
-    KMAP_TRY(exclusive_scan_u32(reinterpret_cast<const uint32_t *>(s->hits), n_seq, s->offs, st));
-    uint64_t total = 0;
-    KMAP_CHECK_HIP(hipMemcpyAsync(&total, s->offs + n_seq, 8, hipMemcpyDeviceToHost, st));
-    KMAP_CHECK_HIP(hipStreamSynchronize(st));
-    KMAP_TRY(kmap_scan_reserve_pos(s, total));
-    if (total)
-        scan_kernel<true><<<grid, KMAP_WAVE * SC_WAVES, 0, st>>>(seq_dev, n, borders_dev, n_seq, k, c, rcc, radius, revcom,
-                                                                 s->hits, s->mind, s->offs, s->pos);
-    KMAP_CHECK_HIP(hipGetLastError());
-    s->total = (int64_t)total;
-    if (total_hits) *total_hits = (int64_t)total;
     return KMAP_OK;
 }
 

@@ -1,4 +1,4 @@
-// scan_util.h -- small shared device utilities (included by counts.hip and scan.hip)
+// scan_util.h -- small shared device utilities: the exclusive scan of uint32 counts (counts*.hip, packed.hip, bitslice.hip, ...)
 #pragma once
 #include "common.h"
 

@@ -1,6 +1,6 @@
 // tests/host_san/driver.cpp -- CPU sanitizer harness for the threaded HOST code of libkmap_hip (test infrastructure, never shipped):
 // the FASTA(.gz) reader and the occurrence-CSV formatter + pwrite pool of kmap_amd/csrc/host_io.hip, and the conversion pool of
-// kmap_amd/csrc/host_pool.h (used by counts.hip's table fetch).  Built twice by the Makefile next to it -- -fsanitize=address,undefined
+// kmap_amd/csrc/host_pool.h (used by counts_io.hip's table fetch).  Built twice by the Makefile next to it -- -fsanitize=address,undefined
 // and -fsanitize=thread -- from the product's own sources compiled host-only; tests/test_host_sanitizers.py drives it.
 //   driver fasta <in.fa[.gz]> <seq.bin> <borders.bin>      arrays as kmap_fasta_open / _read return them
 //   driver csv <out_i32.csv> <out_u8.csv> <n_seq> <seed>    the same synthetic hit lists through both CSV entry points

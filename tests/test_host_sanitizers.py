@@ -1,6 +1,6 @@
 """CPU sanitizer runs of the threaded HOST code of libkmap_hip (round-3 verdict item: none existed).  tests/host_san/Makefile compiles
 kmap_amd/csrc/host_io.hip (FASTA / gz reader, occurrence-CSV formatter + pwrite pool) and kmap_amd/csrc/host_pool.h (the
-conversion pool of counts.hip's table fetch) host-only, once with -fsanitize=address,undefined and once with -fsanitize=thread, into
+conversion pool of counts_io.hip's table fetch) host-only, once with -fsanitize=address,undefined and once with -fsanitize=thread, into
 a small driver; any sanitizer report fails the run (non-zero exit, text on stderr).  The FASTA results are also compared with a
 Python restatement of the reference's array contract (kmer_count.py:244-347) on ragged / empty / CRLF / lowercase / over-long-line
 inputs and with the golden arrays of tests/test.fa.  GPU AddressSanitizer is not available on this pool: CPU only."""

@@ -1,6 +1,6 @@
 """Every KMAP_* environment switch the product reads selects something a test runs (round-3 verdict: ~25 A/B switches selected
 kernels no test ran; the superseded kernels are gone, this file covers the switches that stayed and are not exercised elsewhere:
-KMAP_EMBED_MODE, KMAP_KNN, KMAP_IO_THREADS; KMAP_EMBED_SYM / _GRAPH / KMAP_SEQ_TAIL / _PAIR live in test_gpu_embed.py and
+KMAP_EMBED_MODE, KMAP_KNN, KMAP_IO_THREADS; KMAP_EMBED_SYM / KMAP_SEQ_TAIL / _PAIR live in test_gpu_embed.py and
 test_gpu_fullsize.py, KMAP_DIST_* in test_gpu_distributed.py / test_host_logic.py)."""
 import ctypes as C
 import os

@@ -1,8 +1,6 @@
 #!/usr/bin/env python3
 """Only the neighbour selection at N = 50 000 on a pipeline-like sample (k-mers grouped by label, expanded by counts: many zero-distance
-ties) and on unique sorted k-mers: ms per launch of the kernel KMAP_KNN_SELECT picks (1 one pass, 2 two passes; default by row length),
-checked against a stable argsort on sampled rows.  `knn_select_only.py [n]`"""
-import os
+ties) and on unique sorted k-mers: ms per launch of knn_select_kernel, checked against a stable argsort on sampled rows.  `knn_select_only.py [n]`"""
 import statistics
 import sys
 from pathlib import Path
@@ -55,6 +53,6 @@ for name, (kh, lab, lens) in cases.items():
     for r in rng.integers(0, n, 200):
         drow = D_d.to_numpy(np.uint8, (n,), offset=int(r) * ldd)
         bad += not np.array_equal(got[r], np.sort(np.argsort(drow, kind="stable")[:20]))
-    print(f"KMAP_KNN_SELECT={os.environ.get('KMAP_KNN_SELECT', 'default')} {name}: n={n} {ms:.4f} ms, {n * n / ms / 1e6:.0f} GB/s of N^2, rows differing from the stable argsort: {bad}", flush=True)
+    print(f"{name}: n={n} {ms:.4f} ms, {n * n / ms / 1e6:.0f} GB/s of N^2, rows differing from the stable argsort: {bad}", flush=True)
     for b in (kh_d, lab_d, D_d, nb_d):
         b.free()
