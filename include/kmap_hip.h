@@ -234,6 +234,22 @@ int kmap_scan_result_dev(kmap_scan *s, void **hits_dev, void **pos_dev, int64_t 
 /* hit counts as bytes (narrowed on the device; for lists whose summary max_hits <= 255, larger counts saturate) */
 int kmap_scan_fetch_stream_u8(kmap_scan *s, uint8_t *hits_u8, int32_t *positions, void *stream);
 
+/* ---- position weight matrix scan (scan_pwm; csrc/pwm_scan.hip) -- not in the reference.
+ * Window at array position p, bases x_0 .. x_{width-1}: fwd = sum_j W[x_j][j], rc = sum_j W[3 - x_j][width - 1 - j] (int32, exact).
+ * revcom: score = max(fwd, rc), strand '-' only when rc > fwd; else score = fwd, strand '+'.  A hit is a window without an invalid
+ * position (255 or past the end) whose score is >= threshold; EVERY hit is reported (no per-read minimum rule, no subsample), as
+ * loc = p - start of its read, in read order, ascending inside a read.  The borders must ascend and every valid window must lie in
+ * a read (the encoder's 255 behind every read guarantees it).  4 <= width <= 31 and non-NULL weights, else KMAP_E_INVAL.
+ * Runs on a scan handle: kmap_scan_summary / _fetch_stream / _fetch_stream_u8 / _result_dev serve these lists like a Hamming run's;
+ * there is no per-read minimum distance (kmap_scan_fetch with a non-NULL min_dist returns KMAP_E_STATE until the handle's next
+ * Hamming run).  kmap_pwm_scan_fetch (blocking) adds the scores (int32[total], unit 0.01 bit) and strands; KMAP_E_STATE when the
+ * handle's last run was not a PWM scan. */
+int kmap_pwm_scan_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
+                             const int64_t *borders_dev, int64_t n_seq, int width,
+                             const int32_t *weights /* host, [4][width], rows A C G T */,
+                             int32_t threshold, int revcom, int64_t *total_hits, void *stream);
+int kmap_pwm_scan_fetch(kmap_scan *s, int32_t *hits_per_read, int32_t *positions, int32_t *scores, uint8_t *strand /* 0 '+', 1 '-' */);
+
 /* host-side writer of the occurrence table (gen_motif_occurence_file motif_discovery.py:1396-1419):
  * rows "seq_ind;loc,loc;...;seq_len" for every read with at least one hit; per consensus c the arrays
  * hits[c] (int32[n_seq]) and pos[c] (int32, concatenated in read order, already subsampled/sorted).

@@ -106,6 +106,8 @@ _SIGS = {
     "kmap_scan_fetch_stream_u8": (i32, [vp, vp, vp, vp]),
     "kmap_scan_result_dev": (i32, [vp, P(vp), P(vp), P(i64), P(i64)]),
     "kmap_scan_summary": (i32, [vp, P(i64), P(i32), vp]),
+    "kmap_pwm_scan_packed_dev": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i32, i32, P(i64), vp]),
+    "kmap_pwm_scan_fetch": (i32, [vp, vp, vp, vp, vp]),
     "kmap_write_occurrence_csv": (i32, [C.c_char_p, C.c_char_p, i64, i32, vp, vp, vp, P(i64)]),
     "kmap_write_occurrence_csv_u8": (i32, [C.c_char_p, C.c_char_p, i64, i32, vp, vp, vp, P(i64)]),
     "kmap_write_f2_tsv_line": (i32, [i32, vp, i64]),

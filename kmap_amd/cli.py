@@ -3,8 +3,9 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and `project_kmers`, which the reference does not have: new k-mers placed on the map `visualize_kmers` wrote, without moving
-its points (projection.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+figures), and two verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
+write, with a strand, a score and a p-value threshold per hit (pwm.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -99,3 +100,22 @@ def check_motif_co_occurence(input_fasta_file, motif1, motif2, max_ham_dist1, ma
 def project_kmers(res_dir, kmer_file, output_file=None, n_iter=100):
     from .projection import _project_kmers
     _project_kmers(res_dir, kmer_file, output_file, n_iter)
+
+
+@cli.command(name="scan_pwm")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--matrix_file", type=str, required=True, multiple=True,
+              help="4 x w base-count matrix (rows A, C, G, T; comma-separated, as scan_motif and `ex_hamball --return_type matrix` "
+                   "write them); may be given several times")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="a window is a hit when at most this share of all 4^w sequences scores as high; per strand and per position "
+                   "(not corrected for the two strands or the number of positions)")
+@click.option("--min_score", type=float, default=None, required=False,
+              help="score threshold in bits; replaces the threshold derived from --p_value")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base)")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="score both strands and report the better one (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: pwm_scan in res_dir)")
+def scan_pwm(res_dir, matrix_file, p_value=1e-4, min_score=None, pseudocount=1.0, revcom_mode=None, output_dir=None):
+    from .pwm import _scan_pwm
+    _scan_pwm(res_dir, list(matrix_file), p_value, min_score, pseudocount, revcom_mode, output_dir)

@@ -1378,6 +1378,7 @@ int kmap_scan_run_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint
     KMAP_REQUIRE(n >= 0 && n_seq >= 0 && radius >= 0, "scan_run_packed: negative size");
     s->n_seq = n_seq;
     s->total = 0;
+    s->pwm = 0;
     if (total_hits) *total_hits = 0;
     if (n_seq == 0) return KMAP_OK;
     KMAP_REQUIRE(codes_dev && inval_dev && borders_dev, "scan_run_packed: null pointer");

@@ -84,7 +84,7 @@ int kmap_scan_create(kmap_scan **s) {
 }
 int kmap_scan_destroy(kmap_scan *s) {
     if (!s) return KMAP_OK;
-    void *ptrs[] = {s->hits, s->mind, s->offs, s->pos};
+    void *ptrs[] = {s->hits, s->mind, s->offs, s->pos, s->score, s->strand};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete s;
@@ -154,6 +154,10 @@ int kmap_scan_fetch_stream_u8(kmap_scan *s, uint8_t *hits_u8, int32_t *positions
 
 int kmap_scan_fetch(kmap_scan *s, int32_t *hits_per_read, int8_t *min_dist, int32_t *positions) {
     KMAP_REQUIRE(s, "scan_fetch: null handle");
+    if (s->pwm && min_dist) {
+        kmap_set_error("scan_fetch: a PWM scan has no per-read minimum distance");
+        return KMAP_E_STATE;
+    }
     KMAP_CHECK_HIP(hipDeviceSynchronize());
     if (s->n_seq) {
         if (hits_per_read) KMAP_CHECK_HIP(hipMemcpy(hits_per_read, s->hits, (size_t)s->n_seq * 4, hipMemcpyDeviceToHost));

@@ -1,4 +1,4 @@
-// scan_internal.h -- the occurrence-scan handle shared by scan.hip (uint8 input) and packed.hip (2-bit input)
+// scan_internal.h -- the occurrence-scan handle shared by scan.hip (lists, fetch), packed.hip (Hamming scan) and pwm_scan.hip (PWM scan)
 #pragma once
 #include "common.h"
 
@@ -8,6 +8,11 @@ struct kmap_scan {
     int8_t *mind = nullptr;
     uint64_t *offs = nullptr;           // exclusive scan of hits (run); afterwards scratch: summary words, byte-narrowed hits
     int32_t *pos = nullptr;
+    // a PWM run (pwm_scan.hip) fills hits / pos like a Hamming run, plus a score and a strand per position; it has no per-read minimum distance
+    int pwm = 0;                        // the last run was a PWM scan
+    int32_t *score = nullptr;
+    uint8_t *strand = nullptr;
+    int64_t cap_score = 0;
     // the caller's declaration (kmap_scan_declare_uniform, verified on the device) that read s of these borders is
     // [s * stride, s * stride + len): the per-read kernels then take the borders from s instead of loading 16 bytes per read (bitslice.hip)
     const void *geo_borders = nullptr;

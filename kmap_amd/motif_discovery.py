@@ -218,6 +218,51 @@ class DeviceSeq:
         check(_ffi.lib().kmap_scan_summary(h, C.byref(nhit), C.byref(mx), None))    # returns once the lists are complete
         return ScanHits(self, h, self.n_seq, tot.value, nhit.value, mx.value)
 
+    def _pwm_run(self, h, W, t, revcom):
+        W = np.ascontiguousarray(W, dtype=np.int32)
+        if W.ndim != 2 or W.shape[0] != 4:
+            raise ValueError(f"scan_pwm: weights of shape {W.shape}, expected (4, width) with rows A, C, G, T")
+        if not -2 ** 31 <= int(t) < 2 ** 31:
+            raise ValueError(f"scan_pwm: threshold {t} does not fit int32")
+        tot = _ffi.i64(0)
+        check(_ffi.lib().kmap_pwm_scan_packed_dev(h, self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq,
+                                                  W.shape[1], ptr(W), int(t), int(bool(revcom)), C.byref(tot), None))
+        return tot.value
+
+    def scan_pwm(self, W, t, revcom):
+        """every window of the original reads whose weight-matrix score (W: int32 [4, width], rows A C G T; with revcom the larger
+        of the two strands' scores) is >= t and that touches no invalid position (csrc/pwm_scan.hip):
+        returns (hits_per_read int32[n_seq], positions int32[total], scores int32[total], strand uint8[total]: 0 '+', 1 '-')."""
+        if self._scan is None:
+            h = _ffi.vp()
+            check(_ffi.lib().kmap_scan_create(C.byref(h)))
+            self._scan = h.value
+            self.declare_layout(self._scan)
+        total = self._pwm_run(self._scan, W, t, revcom)
+        hits, pos = np.empty(self.n_seq, np.int32), np.empty(total, np.int32)
+        scores, strand = np.empty(total, np.int32), np.empty(total, np.uint8)
+        check(_ffi.lib().kmap_pwm_scan_fetch(self._scan, ptr(hits), ptr(pos), ptr(scores), ptr(strand)))
+        return hits, pos, scores, strand
+
+    def scan_pwm_lazy(self, W, t, revcom):
+        """scan_pwm() whose (hits_per_read, positions) stay in HBM like scan_lazy()'s: a ScanHits (scores and strands are not kept)"""
+        with self._lazy_lock:
+            h = self._lazy_free.pop() if self._lazy_free else None
+        if h is None:
+            hv = _ffi.vp()
+            check(_ffi.lib().kmap_scan_create(C.byref(hv)))
+            h = hv.value
+            self.declare_layout(h)
+            self._lazy_all.append(h)
+        nhit, mx = _ffi.i64(0), _ffi.i32(0)
+        try:
+            total = self._pwm_run(h, W, t, revcom)
+            check(_ffi.lib().kmap_scan_summary(h, C.byref(nhit), C.byref(mx), None))
+        except BaseException:
+            self._lazy_release(h)
+            raise
+        return ScanHits(self, h, self.n_seq, total, nhit.value, mx.value)
+
     def _lazy_release(self, h):
         with self._lazy_lock:
             if self._lazy_all is not None:

@@ -1,0 +1,361 @@
+"""scan_pwm on the GPU (csrc/pwm_scan.hip) against a numpy restatement of DESIGN.md section 11: sliding windows over the uint8 array,
+W[x, arange(w)].sum(1) for the forward score, the reversed-complemented matrix for the other strand, the borders only to attribute
+hits to reads.  Every comparison is exact integer equality."""
+import ctypes as C
+from pathlib import Path
+
+import numpy as np
+import pytest
+from numpy.lib.stride_tricks import sliding_window_view
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parent.parent
+GOLD = ROOT / "tests" / "golden"
+MOTIF0, MOTIF1 = GOLD / "report_testfa" / "cntmat_motif0_CAATCGATAGC.csv", GOLD / "report_testfa" / "cntmat_motif1_ACCTACGTA.csv"
+
+
+# ---- the restatement -------------------------------------------------------------------------------------------------------
+def window_scores(seq, W):
+    """(valid, fwd, rc) of every window start 0 .. n - w of the uint8 array"""
+    W = np.asarray(W, np.int64)
+    w = W.shape[1]
+    if len(seq) < w:
+        z = np.zeros(0, np.int64)
+        return np.zeros(0, bool), z, z
+    win = sliding_window_view(np.asarray(seq, np.uint8), w)
+    valid = (win != 255).all(axis=1)
+    x = np.where(win == 255, 0, win).astype(np.int64)
+    cols = np.arange(w)
+    fwd = W[x, cols].sum(axis=1)
+    Wrc = W[::-1, ::-1]                                      # Wrc[b][j] = W[3 - b][w - 1 - j]
+    rc = Wrc[x, cols].sum(axis=1)
+    return valid, fwd, rc
+
+
+def np_scan(seq, borders, W, t, revcom, scored=None):
+    """(hits_per_read, loc, score, strand) as section 11 defines them"""
+    valid, fwd, rc = window_scores(seq, W) if scored is None else scored
+    if revcom:
+        score, minus = np.maximum(fwd, rc), rc > fwd        # a tie is '+'
+    else:
+        score, minus = fwd, np.zeros(len(fwd), bool)
+    p = np.nonzero(valid & (score >= t))[0]
+    borders = np.asarray(borders, np.int64).reshape(-1, 2)
+    r = np.searchsorted(borders[:, 0], p, side="right") - 1  # the last read that starts at or before the window
+    assert (p + np.asarray(W).shape[1] <= borders[r, 1]).all()  # a valid window lies inside its read: the 255 behind every read
+    hits = np.bincount(r, minlength=len(borders)).astype(np.int32)
+    return hits, (p - borders[r, 0]).astype(np.int32), score[p].astype(np.int32), minus[p].astype(np.uint8)
+
+
+def make_reads(lengths, rng, frac_invalid=0.02):
+    """reads of the given lengths, a 255 behind each; frac_invalid of the bases are 255, among them first and last bases of reads"""
+    lengths = np.asarray(lengths, np.int64)
+    starts = np.concatenate([[0], np.cumsum(lengths + 1)[:-1]])
+    borders = np.stack([starts, starts + lengths], axis=1)
+    n = int((lengths + 1).sum())
+    seq = rng.integers(0, 4, n).astype(np.uint8)
+    seq[rng.random(n) < frac_invalid] = 255
+    nonempty = np.nonzero(lengths > 0)[0]
+    seq[borders[nonempty[::7], 0]] = 255                     # a read's first base
+    seq[borders[nonempty[3::11], 1] - 1] = 255               # a read's last base
+    seq[borders[:, 1]] = 255
+    return seq, borders
+
+
+def asym_matrix(w, rng):
+    """random weights whose first column strongly wants A and whose last strongly wants C: a wrong column reversal or a wrong
+    complement changes nearly every score"""
+    W = rng.integers(-300, 201, size=(4, w)).astype(np.int32)
+    W[:, 0] = [200, -400, -410, -420]
+    W[:, -1] = [-430, 200, -440, -450]
+    return W
+
+
+def check(got, want):
+    for g, e, name in zip(got, want, ("hits_per_read", "positions", "scores", "strand")):
+        assert g.dtype == e.dtype and g.shape == e.shape, (name, g.dtype, g.shape, e.dtype, e.shape)
+        np.testing.assert_array_equal(g, e, err_msg=name)
+
+
+_CASES = {}
+
+
+def reads_case(w):
+    """~3000 reads per width, built once: (DeviceSeq, seq, borders, W, (valid, fwd, rc))"""
+    if w not in _CASES:
+        from kmap_amd.motif_discovery import DeviceSeq
+        rng = np.random.default_rng(1000 + w)
+        special = [w - 1, w, w + 1, 0, 15, 16, 17, 31, 32, 33, 47, 48]
+        lengths = np.concatenate([special, rng.integers(0, 71, 2990), special[::-1]])
+        lengths = lengths[rng.permutation(len(lengths))]
+        seq, borders = make_reads(lengths, rng)
+        W = asym_matrix(w, rng)
+        _CASES[w] = (DeviceSeq(seq, borders), seq, borders, W, window_scores(seq, W))
+    return _CASES[w]
+
+
+# ---- 1. the kernel against numpy ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("revcom", [True, False])
+@pytest.mark.parametrize("w", [4, 5, 15, 16, 17, 24, 31])
+def test_kernel_against_numpy(w, revcom):
+    ds, seq, borders, W, scored = reads_case(w)
+    valid, fwd, rc = scored
+    score = np.maximum(fwd, rc) if revcom else fwd
+    lo, hi = int(W.min(axis=0).sum()), int(W.max(axis=0).sum())
+    assert valid.sum() > 5000 and not valid.all()
+    t_q = int(np.quantile(score[valid], 0.99))               # about 1 % of the windows
+    for t, kind in ((t_q, "quantile"), (lo, "all"), (hi + 1, "none")):
+        want = np_scan(seq, borders, W, t, revcom, scored)
+        got = ds.scan_pwm(W, t, revcom)
+        check(got, want)
+        n = len(want[1])
+        if kind == "all":
+            assert n == int(valid.sum())
+            if revcom:
+                assert 0 < want[3].sum() < n
+        elif kind == "none":
+            assert n == 0 and got[1].shape == (0,) and not got[0].any()
+        else:
+            assert 0 < n < 0.1 * valid.sum()
+    if not revcom:
+        assert not ds.scan_pwm(W, lo, False)[3].any()
+
+
+# ---- 2. more than 65 535 reads -----------------------------------------------------------------------------------------------
+def test_seventy_thousand_reads():
+    from kmap_amd.motif_discovery import DeviceSeq
+    rng = np.random.default_rng(2)
+    seq, borders = make_reads(np.full(70_000, 20), rng, frac_invalid=0.005)
+    W = asym_matrix(8, rng)
+    scored = window_scores(seq, W)
+    t = int(np.quantile(np.maximum(scored[1], scored[2])[scored[0]], 0.95))
+    want = np_scan(seq, borders, W, t, True, scored)
+    assert 0.03 * scored[0].sum() < len(want[1]) < 0.07 * scored[0].sum() and want[0][65_536:].sum() > 1000
+    ds = DeviceSeq(seq, borders)
+    try:
+        check(ds.scan_pwm(W, t, True), want)
+    finally:
+        ds.close()
+
+
+# ---- 3. a read across many blocks, more than 255 hits in one read -----------------------------------------------------------
+def test_long_read_and_csv_hit_counts(tmp_path):
+    from kmap_amd.locations import read_occurrence
+    from kmap_amd.motif_discovery import DeviceSeq, ScanHits, write_occurence_file
+    rng = np.random.default_rng(3)
+    seq, borders = make_reads([40, 200_000, 0, 35], rng, frac_invalid=0.001)
+    W = asym_matrix(31, rng)
+    scored = window_scores(seq, W)
+    t = int(np.quantile(np.maximum(scored[1], scored[2])[scored[0]], 0.99))
+    want = np_scan(seq, borders, W, t, True, scored)
+    assert want[0][1] > 255 and want[0][2] == 0
+    ds = DeviceSeq(seq, borders)
+    try:
+        got = ds.scan_pwm(W, t, True)
+        check(got, want)
+        lazy = ds.scan_pwm_lazy(W, t, True)                  # the same lists left in HBM, as the occurrence writer takes them
+        assert isinstance(lazy, ScanHits) and lazy.total == len(want[1]) and lazy.max_hits == want[0].max() > 255
+        assert lazy.n_reads_hit == np.count_nonzero(want[0])
+        path = tmp_path / "long.motif_occurence.csv"
+        write_occurence_file([lazy], ["A" * 31], path, ds.out_n_seq, ds.out_read_len)
+        occ = read_occurrence(path)
+        rows = np.nonzero(want[0])[0]
+        np.testing.assert_array_equal(occ.seq_ind, rows)
+        np.testing.assert_array_equal(occ.hits[0], want[0][rows])
+        np.testing.assert_array_equal(occ.pos[0], want[1])
+        np.testing.assert_array_equal(occ.seq_len, (borders[:, 1] - borders[:, 0])[rows])
+    finally:
+        ds.close()
+
+
+# ---- 4. ties never give '-' ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("w", [6, 9, 16])
+def test_self_reverse_complement_matrix_is_all_plus(w):
+    ds, seq, borders, _, _ = reads_case(16 if w == 16 else 15 if w == 9 else 5)
+    rng = np.random.default_rng(40 + w)
+    half = rng.integers(-300, 201, size=(4, w)).astype(np.int32)
+    key = np.arange(w)[None, :] * 4 + np.arange(4)[:, None]   # entry (b, j) and its partner (3 - b, w - 1 - j) get the same weight
+    W = np.ascontiguousarray(np.where(key <= key[::-1, ::-1], half, half[::-1, ::-1]), dtype=np.int32)
+    np.testing.assert_array_equal(W, W[::-1, ::-1])          # equal to its own reverse complement
+    assert len(np.unique(W)) > w
+    valid, fwd, rc = window_scores(seq, W)
+    np.testing.assert_array_equal(fwd, rc)
+    lo = int(W.min(axis=0).sum())
+    for t in (lo, int(np.quantile(fwd[valid], 0.9))):
+        got = ds.scan_pwm(W, t, True)
+        check(got, np_scan(seq, borders, W, t, True, (valid, fwd, rc)))
+        assert len(got[3]) > 100 and not got[3].any()
+        check(ds.scan_pwm(W, t, False), got)                 # and both strands report what the forward strand alone does
+    # fwd == rc on every window without the matrix being its own reverse complement: columns that do not tell the bases apart
+    Wc = np.repeat(rng.integers(-300, 201, size=(1, w)), 4, axis=0).astype(np.int32)
+    got = ds.scan_pwm(Wc, int(Wc[0].sum()), True)
+    assert len(got[1]) == int(window_scores(seq, Wc)[0].sum()) and not got[3].any() and (got[2] == Wc[0].sum()).all()
+    assert len(ds.scan_pwm(Wc, int(Wc[0].sum()) + 1, True)[1]) == 0
+
+
+# ---- 5. the golden reads and matrices ---------------------------------------------------------------------------------------
+# hits, reads with a hit, hits on '-' (both strands), forward-only hits; computed once with the restatement and listed in the issue
+GOLDEN_COUNTS = {
+    ("motif1", 1e-3): (576, 839, 431, None, 484), ("motif1", 1e-4): (1062, 488, 377, 111, 377), ("motif1", 1e-5): (1255, 321, 306, None, 305),
+    ("motif0", 1e-3): (457, 755, 405, None, 410), ("motif0", 1e-4): (962, 507, 374, 133, 374), ("motif0", 1e-5): (1356, 314, 291, None, 291),
+}
+
+
+@pytest.fixture(scope="module")
+def testfa():
+    from kmap_amd.kmer_count import encode_fasta
+    from kmap_amd.motif_discovery import DeviceSeq
+    seq, borders = encode_fasta(str(GOLD / "test.fa"))
+    ds = DeviceSeq(seq, borders)
+    yield ds, np.asarray(seq), np.asarray(borders).reshape(-1, 2)
+    ds.close()
+
+
+@pytest.mark.parametrize("name,path", [("motif0", MOTIF0), ("motif1", MOTIF1)])
+def test_golden_reads(testfa, name, path):
+    from kmap_amd.pwm import pwm_threshold, pwm_weights, read_count_matrix
+    ds, seq, borders = testfa
+    assert len(borders) == 1002
+    W = pwm_weights(read_count_matrix(path))
+    scored = window_scores(seq, W)
+    for p in (1e-3, 1e-4, 1e-5):
+        t_want, n_hits, n_reads, n_minus, n_fwd = GOLDEN_COUNTS[(name, p)]
+        t = pwm_threshold(W, p)[0]
+        assert t == t_want
+        both, fwd_only = np_scan(seq, borders, W, t, True, scored), np_scan(seq, borders, W, t, False, scored)
+        check(ds.scan_pwm(W, t, True), both)                 # the restatement is the arbiter ...
+        check(ds.scan_pwm(W, t, False), fwd_only)
+        assert (len(both[1]), np.count_nonzero(both[0]), len(fwd_only[1])) == (n_hits, n_reads, n_fwd)   # ... the listed counts a second anchor
+        if n_minus is not None:
+            assert int(both[3].sum()) == n_minus
+
+
+# ---- 6. the verb end to end ---------------------------------------------------------------------------------------------------
+def _locations_model(bed_start, hits, pos, width, motif):
+    """DESIGN.md section 9 for one chromosome: per read the windows [start + p, start + p + width] merged where they overlap or touch,
+    rows sorted by (start, end, name as a string)"""
+    rows = []
+    offs = np.concatenate([[0], np.cumsum(hits)])
+    for s in np.nonzero(hits)[0]:
+        merged = []
+        for p in pos[offs[s]:offs[s + 1]]:
+            st, en = int(bed_start[s] + p), int(bed_start[s] + p + width)
+            if not merged or merged[-1][1] < st:
+                merged.append([st, en])
+            else:
+                merged[-1][1] = max(merged[-1][1], en)
+        rows += [["chr1", st, en, f"motif_{motif}_{s}", 0, "+"] for st, en in merged]
+    rows.sort()
+    return "chrom\tstart\tend\tname\tscore\tstrand\n" + "".join("\t".join(map(str, r)) + "\n" for r in rows)
+
+
+def test_verb_end_to_end(tmp_path, testfa, capsys):
+    from kmap_amd.kmer_count import _preproc
+    from kmap_amd.locations import _extract_motif_locations, read_occurrence
+    from kmap_amd.pwm import _scan_pwm, pwm_threshold, pwm_weights, read_count_matrix
+    from kmap_amd.reports import Occurrence
+    _, seq, borders = testfa
+    res = tmp_path / "res"
+    _preproc(str(GOLD / "test.fa"), str(res))
+    files = [str(MOTIF0), str(MOTIF1)]
+    per = _scan_pwm(str(res), files, output_dir=str(tmp_path / "out1"))       # p = 1e-4, a = 1, revcom_mode of the config (true)
+    out = tmp_path / "out1"
+    assert sorted(f.name for f in out.iterdir()) == ["pwm.motif_occurence.csv", "pwm_conseq.txt", "pwm_hits.tsv", "pwm_info.csv"]
+    conseqs = ["CAATCGATAGC", "ACCTACGTA"]
+    assert (out / "pwm_conseq.txt").read_text() == "CAATCGATAGC\nACCTACGTA\n"
+    want, thresholds = [], []
+    for f in files:
+        W = pwm_weights(read_count_matrix(f))
+        t, lo, hi = pwm_threshold(W, 1e-4)
+        thresholds.append((t, lo, hi))
+        want.append(np_scan(seq, borders, W, t, True))
+    for got, exp in zip(per, want):
+        check(got, exp)
+    # the occurrence file: both readers, and the hit lists
+    text = (out / "pwm.motif_occurence.csv").read_text().splitlines()
+    assert text[0] == "seq_ind;motif_0_CAATCGATAGC;motif_1_ACCTACGTA;seq_len"
+    rows = np.nonzero(want[0][0] + want[1][0])[0]
+    assert len(text) == 1 + len(rows)
+    for occ in (read_occurrence(out / "pwm.motif_occurence.csv"), Occurrence.from_file(out / "pwm.motif_occurence.csv")):
+        np.testing.assert_array_equal(occ.seq_ind, rows)
+        np.testing.assert_array_equal(occ.seq_len, (borders[:, 1] - borders[:, 0])[rows])
+        for c in range(2):
+            np.testing.assert_array_equal(occ.hits[c], want[c][0][rows])
+            np.testing.assert_array_equal(occ.pos[c], want[c][1])
+    # pwm_hits.tsv: by motif, read, loc; the score in bits with two decimals
+    lines = (out / "pwm_hits.tsv").read_text().splitlines()
+    assert lines[0] == "motif\tseq_ind\tloc\tstrand\tscore"
+    exp_lines = []
+    for c, (hits, pos, score, strand) in enumerate(want):
+        seq_ind = np.repeat(np.arange(len(hits)), hits)
+        exp_lines += [f"{c}\t{s}\t{p}\t{'-' if m else '+'}\t{'%.2f' % (sc / 100)}" for s, p, sc, m in zip(seq_ind, pos, score, strand)]
+    assert len(exp_lines) == 507 + 488 and lines[1:] == exp_lines
+    # pwm_info.csv
+    info = (out / "pwm_info.csv").read_text().splitlines()
+    assert info[0] == "motif,matrix_file,width,consensus,pseudocount,p_value,threshold,threshold_bits,min_score,max_score,n_hits,n_reads_hit"
+    assert info[1] == f"0,{files[0]},11,CAATCGATAGC,1.0,0.0001,962,9.62,{thresholds[0][1]},{thresholds[0][2]},507,374"
+    assert info[2] == f"1,{files[1]},9,ACCTACGTA,1.0,0.0001,1062,10.62,{thresholds[1][1]},{thresholds[1][2]},488,377"
+    # extract_motif_locations reads the two files as it reads scan_motif's
+    bed_start = 1000 + 500 * np.arange(len(borders), dtype=np.int64)
+    bed = tmp_path / "reads.bed"
+    bed.write_text("".join(f"chr1\t{s}\t{s + 400}\tread{i}\t0\t+\n" for i, s in enumerate(bed_start)))
+    _extract_motif_locations(str(bed), str(out / "pwm_conseq.txt"), str(out / "pwm.motif_occurence.csv"), str(tmp_path / "loc"))
+    assert sorted(f.name for f in (tmp_path / "loc").iterdir()) == [f"motif_{i}_{c}_locations.bed" for i, c in enumerate(conseqs)]
+    for i, c in enumerate(conseqs):
+        assert (tmp_path / "loc" / f"motif_{i}_{c}_locations.bed").read_text() == _locations_model(bed_start, want[i][0], want[i][1], len(c), i)
+    # --min_score in place of the p-value: the same threshold, so the same bytes
+    assert thresholds[0][0] != thresholds[1][0]
+    for i, f in enumerate(files):
+        bits = info[1 + i].split(",")[7]
+        _scan_pwm(str(res), [f], output_dir=str(tmp_path / f"p{i}"))
+        _scan_pwm(str(res), [f], min_score=float(bits), output_dir=str(tmp_path / f"s{i}"))
+        for name in ("pwm.motif_occurence.csv", "pwm_conseq.txt", "pwm_hits.tsv", "pwm_info.csv"):
+            assert (tmp_path / f"s{i}" / name).read_bytes() == (tmp_path / f"p{i}" / name).read_bytes(), name
+    # forward strand only, through the option
+    fwd = _scan_pwm(str(res), files, revcom_mode=False, output_dir=str(tmp_path / "fwd"))
+    assert [len(x[1]) for x in fwd] == [374, 377] and not any(x[3].any() for x in fwd)
+    # a threshold nothing reaches: empty lists, files with headers only, and the verb says so
+    capsys.readouterr()
+    none = _scan_pwm(str(res), [files[1]], min_score=99.0, output_dir=str(tmp_path / "none"))
+    assert len(none[0][1]) == 0 and "no window can reach the threshold" in capsys.readouterr().out
+    assert (tmp_path / "none" / "pwm_hits.tsv").read_text() == "motif\tseq_ind\tloc\tstrand\tscore\n"
+    assert (tmp_path / "none" / "pwm.motif_occurence.csv").read_text() == "seq_ind;motif_0_ACCTACGTA;seq_len\n"
+
+
+# ---- 7. errors and the shared handle ------------------------------------------------------------------------------------------
+def test_errors_and_handle_stays_usable():
+    from kmap_amd import _ffi
+    from kmap_amd.kmer_count import kmer2hash
+    ds, seq, borders, W, scored = reads_case(16)
+    lib = _ffi.lib()
+    before = ds.scan(8, kmer2hash("ACGTACGT"), 2, True)
+    assert before[0].sum() > 0
+    want = np_scan(seq, borders, W, int(np.quantile(scored[1][scored[0]], 0.99)), False, scored)
+    check(ds.scan_pwm(W, int(np.quantile(scored[1][scored[0]], 0.99)), False), want)
+    # after a PWM run the per-read minimum distance does not exist
+    hits, mind, pos = np.empty(ds.n_seq, np.int32), np.empty(ds.n_seq, np.int8), np.empty(len(want[1]), np.int32)
+    assert lib.kmap_scan_fetch(ds._scan, _ffi.ptr(hits), _ffi.ptr(mind), _ffi.ptr(pos)) == -5          # KMAP_E_STATE
+    assert lib.kmap_scan_fetch(ds._scan, _ffi.ptr(hits), None, _ffi.ptr(pos)) == 0
+    np.testing.assert_array_equal(hits, want[0])
+    np.testing.assert_array_equal(pos, want[1])
+    # width outside 4..31, NULL weights: KMAP_E_INVAL, and the last run's lists are still not a Hamming run's
+    tot = _ffi.i64(7)
+    for width in (3, 32):
+        Wb = np.zeros((4, width), np.int32)
+        rc = lib.kmap_pwm_scan_packed_dev(ds._scan, ds.codes.ptr, ds.inval_orig.ptr, ds.n, ds.borders.ptr, ds.n_seq, width, _ffi.ptr(Wb), 0, 1,
+                                          C.byref(tot), None)
+        assert rc == -1 and str(width) in _ffi.last_error()                                            # KMAP_E_INVAL
+        with pytest.raises(ValueError):
+            ds.scan_pwm(Wb, 0, True)
+    assert lib.kmap_pwm_scan_packed_dev(ds._scan, ds.codes.ptr, ds.inval_orig.ptr, ds.n, ds.borders.ptr, ds.n_seq, 8, None, 0, 1,
+                                        C.byref(tot), None) == -1
+    with pytest.raises(ValueError):
+        ds.scan_pwm(np.zeros((3, 8), np.int32), 0, True)
+    # the Hamming scan on the same handle: as before, and its minimum distances are back
+    after = ds.scan(8, kmer2hash("ACGTACGT"), 2, True)
+    np.testing.assert_array_equal(after[0], before[0])
+    np.testing.assert_array_equal(after[1], before[1])
+    assert lib.kmap_scan_fetch(ds._scan, _ffi.ptr(hits), _ffi.ptr(mind), None) == 0
+    # a PWM fetch after a Hamming run is out of order too
+    assert lib.kmap_pwm_scan_fetch(ds._scan, _ffi.ptr(hits), None, None, None) == -5
