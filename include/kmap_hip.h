@@ -250,6 +250,28 @@ int kmap_pwm_scan_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint
                              int32_t threshold, int revcom, int64_t *total_hits, void *stream);
 int kmap_pwm_scan_fetch(kmap_scan *s, int32_t *hits_per_read, int32_t *positions, int32_t *scores, uint8_t *strand /* 0 '+', 1 '-' */);
 
+/* ---- k-mer enrichment against a control table (enrich_kmers; csrc/enrich.hip) -- not in the reference.
+ * Foreground F: any counts handle (its order is kept; it need not ascend).  Control B: a counts handle counted WITHOUT the
+ * reverse-complement merge, keys ascending and unique.  Per foreground entry (x, a): b = B[x] + (revcom ? B[rc x] : 0), a missing key
+ * counts 0 (a palindrome gets 2 B[x], the doubling of merge_revcom kmer_count.py:659-661); D = a Nb - b Nf exactly (128-bit integers),
+ * s = ((a + b)(Nf + Nb - a - b)) ((Nf Nb) / (Nf + Nb)) in double in this order, z = D / sqrt(s), 0 unless s > 0; never NaN.
+ *   set_control  borrows B's arrays (until the next count / load on bg) and builds the bucket directory; asynchronous on stream
+ *   run          b (uint64) and z (double) of every entry of fg (same k, else KMAP_E_INVAL; min_count < 1: KMAP_E_INVAL; a total above
+ *                2^52 - 1: KMAP_E_UNSUP); borrows fg's arrays until the next count / load on fg; asynchronous on stream
+ *   result_dev   device addresses of b and z, n = entries of fg; valid until the handle's next run
+ *   select       blocking: the min(top_n, eligible) entries with a >= min_count ranked by z descending, ties by the lower table
+ *                index -- exact, whatever the size of a tie group (top_n < 1: KMAP_E_INVAL); *n_eligible = entries with a >= min_count
+ *   fetch        the selected rows in rank order: table index, key, a, b (int64), z; any output may be NULL
+ * Calls out of this order, or on a table that was counted again in between, return KMAP_E_STATE. */
+typedef struct kmap_enrich kmap_enrich;
+int kmap_enrich_create(kmap_enrich **e);
+int kmap_enrich_destroy(kmap_enrich *e);
+int kmap_enrich_set_control(kmap_enrich *e, kmap_counts *bg, int revcom, void *stream);
+int kmap_enrich_run(kmap_enrich *e, kmap_counts *fg, int64_t n_fg_total, int64_t n_bg_total, int64_t min_count, void *stream);
+int kmap_enrich_result_dev(kmap_enrich *e, void **b_dev, void **z_dev, int64_t *n);
+int kmap_enrich_select(kmap_enrich *e, int64_t top_n, int64_t *n_sel, int64_t *n_eligible /* optional */, void *stream);
+int kmap_enrich_fetch(kmap_enrich *e, int64_t *idx_out, uint64_t *kh_out, int64_t *a_out, int64_t *b_out, double *z_out);
+
 /* host-side writer of the occurrence table (gen_motif_occurence_file motif_discovery.py:1396-1419):
  * rows "seq_ind;loc,loc;...;seq_len" for every read with at least one hit; per consensus c the arrays
  * hits[c] (int32[n_seq]) and pos[c] (int32, concatenated in read order, already subsampled/sorted).

@@ -108,6 +108,13 @@ _SIGS = {
     "kmap_scan_summary": (i32, [vp, P(i64), P(i32), vp]),
     "kmap_pwm_scan_packed_dev": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i32, i32, P(i64), vp]),
     "kmap_pwm_scan_fetch": (i32, [vp, vp, vp, vp, vp]),
+    "kmap_enrich_create": (i32, [P(vp)]),
+    "kmap_enrich_destroy": (i32, [vp]),
+    "kmap_enrich_set_control": (i32, [vp, vp, i32, vp]),
+    "kmap_enrich_run": (i32, [vp, vp, i64, i64, i64, vp]),
+    "kmap_enrich_result_dev": (i32, [vp, P(vp), P(vp), P(i64)]),
+    "kmap_enrich_select": (i32, [vp, i64, P(i64), P(i64), vp]),
+    "kmap_enrich_fetch": (i32, [vp, vp, vp, vp, vp, vp]),
     "kmap_write_occurrence_csv": (i32, [C.c_char_p, C.c_char_p, i64, i32, vp, vp, vp, P(i64)]),
     "kmap_write_occurrence_csv_u8": (i32, [C.c_char_p, C.c_char_p, i64, i32, vp, vp, vp, P(i64)]),
     "kmap_write_f2_tsv_line": (i32, [i32, vp, i64]),

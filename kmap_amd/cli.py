@@ -3,9 +3,11 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and two verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+figures), and three verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
 its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
-write, with a strand, a score and a p-value threshold per hit (pwm.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+write, with a strand, a score and a p-value threshold per hit (pwm.py), and `enrich_kmers`, the k-mers and motifs of a result
+directory scored against control reads instead of the uniform null: both read sets counted on the GPU, the tables joined there, a
+pooled two-proportion z per k-mer and an exact top-N selection (enrichment.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -119,3 +121,20 @@ def project_kmers(res_dir, kmer_file, output_file=None, n_iter=100):
 def scan_pwm(res_dir, matrix_file, p_value=1e-4, min_score=None, pseudocount=1.0, revcom_mode=None, output_dir=None):
     from .pwm import _scan_pwm
     _scan_pwm(res_dir, list(matrix_file), p_value, min_score, pseudocount, revcom_mode, output_dir)
+
+
+@cli.command(name="enrich_kmers")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--control_fasta_file", type=str, required=True,
+              help="FASTA file of the control reads (input DNA, flanks, round 0, shuffled reads); counted like the reads of res_dir")
+@click.option("--kmer_len", type=int, multiple=True, required=False,
+              help="k-mer length to rank, 1..31; may be given several times (default: none, the motif table only)")
+@click.option("--top_n", type=int, default=1000, required=False, help="rows per enriched_kmers_k{k}.tsv: the k-mers with the largest z")
+@click.option("--min_count", type=int, default=2, required=False, help="smallest foreground count of a ranked k-mer")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount of the log2 fold change")
+@click.option("--conseq_file", type=str, default=None, required=False,
+              help="consensus sequences, one per line, for motif_enrichment.csv (default: final_conseq.txt in res_dir, when it exists)")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: kmer_enrichment in res_dir)")
+def enrich_kmers(res_dir, control_fasta_file, kmer_len=(), top_n=1000, min_count=2, pseudocount=1.0, conseq_file=None, output_dir=None):
+    from .enrichment import _enrich_kmers
+    _enrich_kmers(res_dir, control_fasta_file, list(kmer_len), top_n, min_count, pseudocount, conseq_file, output_dir)
