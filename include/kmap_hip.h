@@ -250,6 +250,20 @@ int kmap_pwm_scan_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint
                              int32_t threshold, int revcom, int64_t *total_hits, void *stream);
 int kmap_pwm_scan_fetch(kmap_scan *s, int32_t *hits_per_read, int32_t *positions, int32_t *scores, uint8_t *strand /* 0 '+', 1 '-' */);
 
+/* ---- one iteration of the weight-matrix refinement (refine_pwm; csrc/pwm_refine.hip) -- not in the reference.
+ * The hits are those of kmap_pwm_scan_packed_dev for the same arguments (same argument rules; select_best must be 0 or 1, counts
+ * non-NULL, else KMAP_E_INVAL).  select_best 0: every hit is selected; 1: per read the hit with the largest score, on a tie the
+ * smallest loc.  counts[b][j] = the number of selected windows whose oriented base j is b: window base j on '+', 3 - (window base
+ * width - 1 - j) on '-'.  *n_hits = all hits, *n_selected = selected windows (= every column sum of counts), *n_minus = selected
+ * windows on '-' (each may be NULL).  Blocking; integer arithmetic only, so two calls give the same numbers.  It works in scratch
+ * memory: no scan handle is needed, and none is touched.  n_seq == 0 or n == 0 gives zeros. */
+int kmap_refine_counts_packed_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
+                                  const int64_t *borders_dev, int64_t n_seq, int width,
+                                  const int32_t *weights /* host, [4][width], rows A C G T */,
+                                  int32_t threshold, int revcom, int select_best,
+                                  int64_t *counts /* host, [4][width], rows A C G T */,
+                                  int64_t *n_hits, int64_t *n_selected, int64_t *n_minus, void *stream);
+
 /* ---- k-mer enrichment against a control table (enrich_kmers; csrc/enrich.hip) -- not in the reference.
  * Foreground F: any counts handle (its order is kept; it need not ascend).  Control B: a counts handle counted WITHOUT the
  * reverse-complement merge, keys ascending and unique.  Per foreground entry (x, a): b = B[x] + (revcom ? B[rc x] : 0), a missing key

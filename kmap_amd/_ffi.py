@@ -108,6 +108,7 @@ _SIGS = {
     "kmap_scan_summary": (i32, [vp, P(i64), P(i32), vp]),
     "kmap_pwm_scan_packed_dev": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i32, i32, P(i64), vp]),
     "kmap_pwm_scan_fetch": (i32, [vp, vp, vp, vp, vp]),
+    "kmap_refine_counts_packed_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, i32, i32, i32, vp, P(i64), P(i64), P(i64), vp]),
     "kmap_enrich_create": (i32, [P(vp)]),
     "kmap_enrich_destroy": (i32, [vp]),
     "kmap_enrich_set_control": (i32, [vp, vp, i32, vp]),

@@ -3,11 +3,12 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and three verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+figures), and four verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
 its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
 write, with a strand, a score and a p-value threshold per hit (pwm.py), and `enrich_kmers`, the k-mers and motifs of a result
 directory scored against control reads instead of the uniform null: both read sets counted on the GPU, the tables joined there, a
-pooled two-proportion z per k-mer and an exact top-N selection (enrichment.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+pooled two-proportion z per k-mer and an exact top-N selection (enrichment.py), and `refine_pwm`, a count matrix iterated on the
+reads -- scan, select, count the selected windows' bases -- until it reproduces itself (refine.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -121,6 +122,30 @@ def project_kmers(res_dir, kmer_file, output_file=None, n_iter=100):
 def scan_pwm(res_dir, matrix_file, p_value=1e-4, min_score=None, pseudocount=1.0, revcom_mode=None, output_dir=None):
     from .pwm import _scan_pwm
     _scan_pwm(res_dir, list(matrix_file), p_value, min_score, pseudocount, revcom_mode, output_dir)
+
+
+@cli.command(name="refine_pwm")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--matrix_file", type=str, required=True, multiple=True,
+              help="4 x w base-count matrix to start from (rows A, C, G, T; comma-separated, as scan_motif and `ex_hamball "
+                   "--return_type matrix` write them); may be given several times")
+@click.option("--flank", type=int, default=0, required=False,
+              help="empty columns added on each side before the first iteration (width + 2 x flank <= 31)")
+@click.option("--select", type=click.Choice(["best", "all"]), default="best", required=False,
+              help="windows counted per iteration: the best hit of every read (ties: the smallest loc), or every hit -- on a motif "
+                   "with a reverse-palindromic core `all` counts both strands of one site and drifts")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="hit threshold of every iteration, as scan_pwm's: per strand and per position")
+@click.option("--pseudocount", type=float, default=1.0, required=False,
+              help="pseudocount added to every column (a quarter per base); must be > 0 with --flank")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="score both strands and count the better one (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--max_iter", type=int, default=20, required=False, help="largest number of iterations")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: pwm_refine in res_dir)")
+def refine_pwm(res_dir, matrix_file, flank=0, select="best", p_value=1e-4, pseudocount=1.0, revcom_mode=None, max_iter=20,
+               output_dir=None):
+    from .refine import _refine_pwm
+    _refine_pwm(res_dir, list(matrix_file), flank, select, p_value, pseudocount, revcom_mode, max_iter, output_dir)
 
 
 @cli.command(name="enrich_kmers")

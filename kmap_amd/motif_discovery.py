@@ -263,6 +263,22 @@ class DeviceSeq:
             raise
         return ScanHits(self, h, self.n_seq, total, nhit.value, mx.value)
 
+    def pwm_counts(self, W, t, revcom, select_best=True):
+        """one refinement step (csrc/pwm_refine.hip): of scan_pwm(W, t, revcom)'s hits on the original reads,
+        every one (select_best False) or per read the one with the largest score, the smallest loc on a tie; returns
+        (C' int64[4, width]: C'[b][j] = selected windows whose oriented base j is b, n_hits, n_selected, n_minus).  Needs no scan handle."""
+        W = np.ascontiguousarray(W, dtype=np.int32)
+        if W.ndim != 2 or W.shape[0] != 4:
+            raise ValueError(f"pwm_counts: weights of shape {W.shape}, expected (4, width) with rows A, C, G, T")
+        if not -2 ** 31 <= int(t) < 2 ** 31:
+            raise ValueError(f"pwm_counts: threshold {t} does not fit int32")
+        counts = np.zeros((4, W.shape[1]), np.int64)
+        n_hits, n_sel, n_minus = _ffi.i64(0), _ffi.i64(0), _ffi.i64(0)
+        check(_ffi.lib().kmap_refine_counts_packed_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq,
+                                                       W.shape[1], ptr(W), int(t), int(bool(revcom)), int(bool(select_best)), ptr(counts),
+                                                       C.byref(n_hits), C.byref(n_sel), C.byref(n_minus), None))
+        return counts, n_hits.value, n_sel.value, n_minus.value
+
     def _lazy_release(self, h):
         with self._lazy_lock:
             if self._lazy_all is not None:
