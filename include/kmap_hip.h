@@ -423,7 +423,8 @@ int kmap_hamdist_matrix_u8(const uint64_t *kh, const int32_t *label, int64_t n, 
 /* ---- kNN smoothing: knn_smooth visualization.py:90-109, kernel taichi_core.py:227-249
  * integer form: sums[i,j] = sum_{a in nb[i], b in nb[j]} D[a,b]  (exact; S = f32(sums)/n_nb/n_nb),
  * diagonal forced to 0.  D: uint8 rows [0,n) with leading dimension ldd; nb: int32 [n, n_nb];
- * writes uint16 rows [row0,row0+nrows) with leading dimension lds. */
+ * writes uint16 rows [row0,row0+nrows) with leading dimension lds.  n_nb^2 * max(D) must fit the uint16 sums: KMAP_E_UNSUP
+ * (nothing written) above 65535. */
 int kmap_knn_sums_u8_dev(const uint8_t *D_dev, int64_t ldd, const int32_t *nb_dev, int64_t n, int n_nb,
                          int64_t row0, int64_t nrows, uint16_t *sums_dev, int64_t lds, void *stream);
 /* the same sums straight from the k-mers, without reading D: the double sum over neighbour pairs of mismatching bases is

@@ -307,7 +307,7 @@ int knn_sums_kmers(const H *kh_dev, const int32_t *label_dev, int64_t n, int k, 
     const int zero_diag = (n_nb & KMAP_KNN_NATURAL_DIAG) ? 0 : 1;
     n_nb &= ~KMAP_KNN_NATURAL_DIAG;
     KMAP_REQUIRE(n >= 0 && nrows >= 0 && row0 >= 0 && row0 + nrows <= n, "knn_sums_kmers: bad row range");
-    KMAP_REQUIRE(n_nb > 0 && n_nb <= 255 && lds >= n, "knn_sums_kmers: bad n_nb / leading dimension");
+    KMAP_REQUIRE(n_nb > 0 && lds >= n, "knn_sums_kmers: bad n_nb / leading dimension");   // n_nb > 255: refused below (n_nb^2 k > 65535)
     KMAP_REQUIRE(n_lab >= 0 && n_lab <= 255 && (n_lab == 0 || clen), "knn_sums_kmers: bad label table");
     if (k < 1 || k > 16 || (int64_t)n_nb * n_nb * k > 65535) {
         kmap_set_error("knn_sums_kmers: k=%d, n_nb=%d outside the profile kernel's range (use the matrix-based entry point)", k, n_nb);

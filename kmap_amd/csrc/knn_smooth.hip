@@ -475,6 +475,10 @@ int kmap_knn_sums_u8_dev(const uint8_t *D_dev, int64_t ldd, const int32_t *nb_de
         max_u8_kernel<<<2048, 256, 0, st>>>(D_dev, ldd, n, dmax_dev);
         KMAP_CHECK_HIP(hipMemcpyAsync(&dmax, dmax_dev, 4, hipMemcpyDeviceToHost, st));
         KMAP_CHECK_HIP(hipStreamSynchronize(st));
+        if ((uint64_t)n_nb * (uint64_t)n_nb * (uint64_t)dmax > 65535u) {   // the uint16 sums would wrap
+            kmap_set_error("knn_sums: n_nb^2 * max(D) = %d^2 * %u exceeds the 65535 a uint16 sum holds (use the float operator)", n_nb, dmax);
+            return KMAP_E_UNSUP;
+        }
         const bool m8 = (uint64_t)dmax * (uint64_t)n_nb <= 255u;
         const int64_t mpitch = (n + 15) & ~(int64_t)15;
         const int64_t row_bytes = mpitch * (m8 ? 1 : 2);

@@ -152,7 +152,8 @@ def _is_small_int_matrix(m):
 
 def knn_sums_dev(D_dev_ptr, ldd, nb, n, n_nb, row0=0, nrows=None, stream=None, out=None):
     """Device: integer neighbour sums of rows [row0,row0+nrows) -> DeviceBuffer of uint16 [nrows x lds]
-    (out: device address of a caller-owned block to fill instead; the returned buffer is then None)."""
+    (out: device address of a caller-owned block to fill instead; the returned buffer is then None).
+    Raises KmapError when n_nb^2 * max(D) > 65535: the sums would not fit (Hamming matrices of k <= 31 with 20 neighbours do)."""
     nrows = n - row0 if nrows is None else nrows
     lds = (n + 127) & ~127
     own = not isinstance(nb, _ffi.DeviceBuffer)
@@ -249,7 +250,8 @@ def knn_smooth(dist_mat: np.ndarray, n_neighbour: int, neighbor_inds_mat=None) -
     if neighbor_inds_mat is None:
         neighbor_inds_mat = np.argpartition(dist_mat, n_neighbour, axis=1)[:, :n_neighbour]
     nb = np.ascontiguousarray(neighbor_inds_mat, np.int32)
-    if _is_small_int_matrix(dist_mat):
+    # the integer path holds its sums in uint16: beyond n_nb^2 * max(D) = 65535 the float operator below takes the matrix
+    if _is_small_int_matrix(dist_mat) and n_neighbour * n_neighbour * int(dist_mat.max()) <= 65535:
         ldd = pitch_for(n)
         D_d = _ffi.DeviceBuffer.from_numpy(_pad_cols(np.ascontiguousarray(dist_mat, np.uint8), ldd))
         sums_d, lds = knn_sums_dev(D_d.ptr, ldd, nb, n, n_neighbour)

@@ -54,6 +54,36 @@ def test_status_codes_and_last_error():
         _ffi.check(-1)
 
 
+def test_knn_sums_refuses_sums_beyond_uint16():
+    """n_nb^2 * max(D) > 65535 cannot be held by the uint16 sums: KMAP_E_UNSUP naming the three numbers, nothing written -- not
+    wrapped sums.  One step below the limit the same call runs."""
+    from kmap_amd import _ffi
+    L = _ffi.lib()
+    n, n_nb = 16, 20
+    D = np.full((n, n), 163, np.uint8)                                  # 400 * 163 = 65 200
+    nb_d = _ffi.DeviceBuffer.from_numpy(np.zeros((n, n_nb), np.int32))
+    out_d = _ffi.DeviceBuffer(n * n * 2)
+    _ffi.check(L.kmap_memset(out_d.ptr, 0xA5, n * n * 2, None))
+    D_d = _ffi.DeviceBuffer.from_numpy(D)
+    assert L.kmap_knn_sums_u8_dev(D_d.ptr, n, nb_d.ptr, n, n_nb, 0, n, out_d.ptr, n, None) == 0
+    _ffi.sync()
+    got = out_d.to_numpy(np.uint16, (n, n))
+    assert np.all(got[~np.eye(n, dtype=bool)] == 65200) and not got.diagonal().any()
+    D[3, 5] = 164                                                       # 400 * 164 = 65 600
+    D_d.free()
+    D_d = _ffi.DeviceBuffer.from_numpy(D)
+    _ffi.check(L.kmap_memset(out_d.ptr, 0xA5, n * n * 2, None))
+    rc = L.kmap_knn_sums_u8_dev(D_d.ptr, n, nb_d.ptr, n, n_nb, 0, n, out_d.ptr, n, None)
+    msg = L.kmap_last_error()
+    assert rc == -4 and b"20" in msg and b"164" in msg and b"65535" in msg, (rc, msg)
+    _ffi.sync()
+    assert np.all(out_d.to_numpy(np.uint8, (n * n * 2,)) == 0xA5)
+    with pytest.raises(_ffi.KmapError):
+        _ffi.check(rc)
+    for b in (D_d, nb_d, out_d):
+        b.free()
+
+
 def test_empty_inputs_are_fine():
     import kmap_amd.kmer_count as K
     from kmap_amd.hamdist import hamdist_matrix_u8
