@@ -264,6 +264,25 @@ int kmap_refine_counts_packed_dev(const uint32_t *codes_dev, const uint16_t *inv
                                   int64_t *counts /* host, [4][width], rows A C G T */,
                                   int64_t *n_hits, int64_t *n_selected, int64_t *n_minus, void *stream);
 
+/* ---- the best window of every read under a weight matrix (evaluate_pwm; csrc/pwm_readscore.hip) -- not in the
+ * reference.  Scores, strands and valid windows are those of kmap_pwm_scan_packed_dev (same argument rules: 4 <= width <= 31,
+ * non-NULL weights, sizes >= 0, else KMAP_E_INVAL; the borders ascend and every valid window lies in a read); there is no threshold.
+ * Per read: among its valid windows the largest score, on a tie the smallest loc; score_dev[r] (unit 0.01 bit), loc_dev[r] = the
+ * window's first position - the read's start, strand_dev[r] = 0 '+' / 1 '-' (section 11's, '-' only when rc > fwd).  A read without
+ * a valid window (empty, shorter than width, an invalid base in every window) gets INT32_MIN, -1, 0.  The three arrays are the
+ * caller's device arrays of n_seq elements; *n_scored (may be NULL) = reads with a valid window.  Blocking; integer maxima only, so
+ * two calls give the same arrays.  It works in scratch memory: no scan handle is needed, and none is touched.  n_seq == 0 writes
+ * nothing; n == 0 marks every read unscorable. */
+int kmap_readscore_packed_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
+                              const int64_t *borders_dev, int64_t n_seq, int width,
+                              const int32_t *weights /* host, [4][width], rows A C G T */, int revcom,
+                              int32_t *score_dev, int32_t *loc_dev, uint8_t *strand_dev, int64_t *n_scored, void *stream);
+/* hist_host[s - lo] = the number of reads with loc_dev[r] >= 0 and score_dev[r] = s, for lo <= s < lo + n_bins (host, uint64);
+ * *n_outside (may be NULL) = reads with loc_dev[r] >= 0 whose score lies outside that range (they are in no bin).  Blocking.
+ * n_bins > 2^22: KMAP_E_UNSUP; a negative size or a NULL array: KMAP_E_INVAL. */
+int kmap_readscore_hist_dev(const int32_t *score_dev, const int32_t *loc_dev, int64_t n_seq, int32_t lo, int64_t n_bins,
+                            uint64_t *hist_host, int64_t *n_outside, void *stream);
+
 /* ---- k-mer enrichment against a control table (enrich_kmers; csrc/enrich.hip) -- not in the reference.
  * Foreground F: any counts handle (its order is kept; it need not ascend).  Control B: a counts handle counted WITHOUT the
  * reverse-complement merge, keys ascending and unique.  Per foreground entry (x, a): b = B[x] + (revcom ? B[rc x] : 0), a missing key

@@ -3,12 +3,14 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and four verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+figures), and five verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
 its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
 write, with a strand, a score and a p-value threshold per hit (pwm.py), and `enrich_kmers`, the k-mers and motifs of a result
 directory scored against control reads instead of the uniform null: both read sets counted on the GPU, the tables joined there, a
 pooled two-proportion z per k-mer and an exact top-N selection (enrichment.py), and `refine_pwm`, a count matrix iterated on the
-reads -- scan, select, count the selected windows' bases -- until it reproduces itself (refine.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+reads -- scan, select, count the selected windows' bases -- until it reproduces itself (refine.py), and `evaluate_pwm`, the best
+window score of every read and of every control read under a count matrix, compared by a rank statistic (AUROC, Mann-Whitney z) and
+by the two-proportion z at every score threshold (evaluate.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -163,3 +165,28 @@ def refine_pwm(res_dir, matrix_file, flank=0, select="best", p_value=1e-4, pseud
 def enrich_kmers(res_dir, control_fasta_file, kmer_len=(), top_n=1000, min_count=2, pseudocount=1.0, conseq_file=None, output_dir=None):
     from .enrichment import _enrich_kmers
     _enrich_kmers(res_dir, control_fasta_file, list(kmer_len), top_n, min_count, pseudocount, conseq_file, output_dir)
+
+
+@cli.command(name="evaluate_pwm")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--control_fasta_file", type=str, required=True,
+              help="FASTA file of the control reads (input DNA, flanks, round 0, shuffled reads); scored like the reads of res_dir")
+@click.option("--matrix_file", type=str, required=True, multiple=True,
+              help="4 x w base-count matrix (rows A, C, G, T; comma-separated, as scan_motif, `ex_hamball --return_type matrix` and "
+                   "refine_pwm write them); may be given several times")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="the reads above scan_pwm's threshold of this p-value are compared too (per strand and per position)")
+@click.option("--min_score", type=float, default=None, required=False,
+              help="score threshold in bits; replaces the threshold derived from --p_value")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base)")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="score both strands and keep the better one (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--min_reads", type=int, default=10, required=False,
+              help="the best threshold is sought among those that at least this many reads (of both sets together) reach")
+@click.option("--read_scores", is_flag=True, default=False, help="also write the best score, loc and strand of every read")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: pwm_eval in res_dir)")
+def evaluate_pwm(res_dir, control_fasta_file, matrix_file, p_value=1e-4, min_score=None, pseudocount=1.0, revcom_mode=None,
+                 min_reads=10, read_scores=False, output_dir=None):
+    from .evaluate import _evaluate_pwm
+    _evaluate_pwm(res_dir, control_fasta_file, list(matrix_file), p_value, min_score, pseudocount, revcom_mode, min_reads, read_scores,
+                  output_dir)

@@ -279,6 +279,25 @@ class DeviceSeq:
                                                        C.byref(n_hits), C.byref(n_sel), C.byref(n_minus), None))
         return counts, n_hits.value, n_sel.value, n_minus.value
 
+    def read_scores(self, W, revcom):
+        """per read the valid window with the largest score, on a tie the smallest loc (csrc/pwm_readscore.hip, DESIGN.md section
+        14; scores and strands are scan_pwm's, there is no threshold): a ReadScores whose three arrays stay in HBM until fetch().
+        Needs no scan handle."""
+        W = np.ascontiguousarray(W, dtype=np.int32)
+        if W.ndim != 2 or W.shape[0] != 4:
+            raise ValueError(f"read_scores: weights of shape {W.shape}, expected (4, width) with rows A, C, G, T")
+        out = ReadScores(self.n_seq)
+        try:
+            n_scored = _ffi.i64(0)
+            check(_ffi.lib().kmap_readscore_packed_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq,
+                                                       W.shape[1], ptr(W), int(bool(revcom)), out.score.ptr, out.loc.ptr, out.strand.ptr,
+                                                       C.byref(n_scored), None))
+        except BaseException:
+            out.close()
+            raise
+        out.n_scored = n_scored.value
+        return out
+
     def _lazy_release(self, h):
         with self._lazy_lock:
             if self._lazy_all is not None:
@@ -293,6 +312,40 @@ class DeviceSeq:
         for h in handles:                 # a ScanHits not fetched by now reports that its sequence is closed
             _ffi.lib().kmap_scan_destroy(h)
         for b in (self.codes, self.planes, self.inval_orig, self.inval_work, self.borders):
+            b.free()
+
+
+class ReadScores:
+    """DeviceSeq.read_scores' result in HBM: score int32[n_seq] (unit 0.01 bit), loc int32[n_seq], strand uint8[n_seq] (0 '+', 1 '-');
+    a read without a valid window has INT32_MIN, -1, 0.  `n_scored` = reads with a valid window."""
+    MAX_BINS = 1 << 22
+
+    def __init__(self, n_seq):
+        self.n_seq, self.n_scored = int(n_seq), 0
+        self.score, self.loc = _ffi.DeviceBuffer(max(self.n_seq, 1) * 4), _ffi.DeviceBuffer(max(self.n_seq, 1) * 4)
+        self.strand = _ffi.DeviceBuffer(max(self.n_seq, 1))
+
+    def fetch(self):
+        """(score, loc, strand) as numpy arrays"""
+        out = (self.score.to_numpy(np.int32, (self.n_seq,)), self.loc.to_numpy(np.int32, (self.n_seq,)),
+               self.strand.to_numpy(np.uint8, (self.n_seq,)))
+        _ffi.sync()
+        return out
+
+    def histogram(self, lo, n_bins):
+        """uint64[n_bins]: the number of scorable reads with best score lo + i; ValueError when n_bins is more than 2^22 or a
+        scorable read's score lies outside [lo, lo + n_bins)"""
+        lo, n_bins = int(lo), int(n_bins)
+        if not 0 <= n_bins <= self.MAX_BINS or not -2 ** 31 <= lo < 2 ** 31:
+            raise ValueError(f"read score histogram: {n_bins} bins from {lo}, at most 2^22 bins of int32 scores are supported")
+        hist, outside = np.zeros(n_bins, np.uint64), _ffi.i64(0)
+        check(_ffi.lib().kmap_readscore_hist_dev(self.score.ptr, self.loc.ptr, self.n_seq, lo, n_bins, ptr(hist), C.byref(outside), None))
+        if outside.value:
+            raise ValueError(f"read score histogram: {outside.value} reads score outside [{lo}, {lo + n_bins})")
+        return hist
+
+    def close(self):
+        for b in (self.score, self.loc, self.strand):
             b.free()
 
 
