@@ -421,6 +421,19 @@ int kmap_synth_reads_dev(uint8_t *seq_dev, int64_t *borders_dev, int64_t n_reads
                          const uint8_t *motif_codes, const int32_t *motif_len, const double *fractions, int n_motifs,
                          double mutation_rate, void *stream);
 
+/* ---- k-let-preserving shuffle of the packed reads (shuffle_reads; csrc/shuffle.hip) -- not in the reference.
+ * A segment is a maximal run of valid positions of the array; invalid positions (255: N, separators) keep their place and their
+ * value.  Every segment is shuffled on its own.  klet 1: uniform over the arrangements of its bases.  klet 2: uniform over the
+ * sequences with the same first base and the same 16 dinucleotide counts (hence the same last base); segments of at most 3 bases
+ * come back unchanged.  Every random draw is a function of (seed, array position of the segment's first base, draw index) alone
+ * -- section 15 has the formulas --, so two calls give the same bytes on any launch shape.  seq_out_dev: uint8[n] in the array
+ * contract (kmap_pack_reads_dev packs it again); the packed arrays hold kmap_packed_groups(n) groups.  stats (host, may be NULL):
+ * stats[0] = segments, stats[1] = valid bases.  klet other than 1 or 2, n < 0 or a NULL array: KMAP_E_INVAL.  A segment of more
+ * than 2^21 - 1 bases: KMAP_E_UNSUP, and nothing is written to seq_out_dev.  n == 0 is a no-op.  The call blocks until the
+ * segment list is built and checked; the kernels that write seq_out_dev are asynchronous on `stream`. */
+int kmap_shuffle_packed_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, int klet, uint64_t seed,
+                            uint8_t *seq_out_dev, int64_t *stats /* optional: segments, valid bases */, void *stream);
+
 /* ---- all-pairs Hamming matrix: cal_samp_kmer_hamdist_mat motif_discovery.py:759-808
  * (one launch instead of n_uniq launches + Python block expansion).  kh: N hashes (already
  * expanded by counts), label: N int32; pairs sharing label l with clen[l] < k are compared on the

@@ -136,6 +136,7 @@ _SIGS = {
     "kmap_bed_close": (i32, [vp]),
     "kmap_locations_sort": (i32, [i64, i32, vp, vp, vp, vp, vp, i64, vp, vp, i32, i64, vp, vp, vp, vp, P(f32)]),
     "kmap_synth_reads_dev": (i32, [vp, vp, i64, i32, C.c_uint64, vp, vp, vp, i32, C.c_double, vp]),
+    "kmap_shuffle_packed_dev": (i32, [vp, vp, i64, i32, u64, vp, P(i64), vp]),
     "kmap_hamdist_matrix_u32_dev": (i32, [vp, vp, i64, i32, vp, i32, i64, i64, vp, i64, vp]),
     "kmap_hamdist_matrix_u64_dev": (i32, [vp, vp, i64, i32, vp, i32, i64, i64, vp, i64, vp]),
     "kmap_hamdist_matrix_u8": (i32, [vp, vp, i64, i32, vp, i32, vp]),

@@ -3,14 +3,15 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and five verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+figures), and six verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
 its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
 write, with a strand, a score and a p-value threshold per hit (pwm.py), and `enrich_kmers`, the k-mers and motifs of a result
 directory scored against control reads instead of the uniform null: both read sets counted on the GPU, the tables joined there, a
 pooled two-proportion z per k-mer and an exact top-N selection (enrichment.py), and `refine_pwm`, a count matrix iterated on the
 reads -- scan, select, count the selected windows' bases -- until it reproduces itself (refine.py), and `evaluate_pwm`, the best
 window score of every read and of every control read under a count matrix, compared by a rank statistic (AUROC, Mann-Whitney z) and
-by the two-proportion z at every score threshold (evaluate.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+by the two-proportion z at every score threshold (evaluate.py), and `shuffle_reads`, the control reads for those two when there is
+no second read set: every read shuffled on the GPU so that its length, its N and its base or dinucleotide counts stay (shuffle.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -190,3 +191,16 @@ def evaluate_pwm(res_dir, control_fasta_file, matrix_file, p_value=1e-4, min_sco
     from .evaluate import _evaluate_pwm
     _evaluate_pwm(res_dir, control_fasta_file, list(matrix_file), p_value, min_score, pseudocount, revcom_mode, min_reads, read_scores,
                   output_dir)
+
+
+@cli.command(name="shuffle_reads")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds the encoded reads)")
+@click.option("--klet", type=int, default=2, required=False,
+              help="what every read keeps: 1 its base counts, 2 its first base and its dinucleotide counts (hence its last base)")
+@click.option("--seed", type=int, default=0, required=False, help="0 .. 2^64 - 1; the same seed writes the same file")
+@click.option("--n_copies", type=int, default=1, required=False, help="shuffled copies of every read, written copy after copy")
+@click.option("--output_file", type=str, default=None, required=False,
+              help="output FASTA file (default: shuffled_control.fa in res_dir), a --control_fasta_file for enrich_kmers / evaluate_pwm")
+def shuffle_reads(res_dir, klet=2, seed=0, n_copies=1, output_file=None):
+    from .shuffle import _shuffle_reads
+    _shuffle_reads(res_dir, klet, seed, n_copies, output_file)

@@ -298,6 +298,37 @@ class DeviceSeq:
         out.n_scored = n_scored.value
         return out
 
+    def shuffled(self, klet=2, seed=0):
+        """a new resident read set: every maximal run of valid bases of the ORIGINAL reads (inval_orig; a mask() before does not
+        count) shuffled so that its base counts (klet 1) or its first base and dinucleotide counts (klet 2) stay (csrc/shuffle.hip,
+        DESIGN.md section 15).  The result has its own copy of the borders; this object is not touched.  `shuffle_stats` of the
+        result = (segments, valid bases)."""
+        if isinstance(klet, bool) or int(klet) != klet or int(klet) not in (1, 2):
+            raise ValueError(f"shuffled: klet {klet}: 1 (base counts) or 2 (dinucleotide counts) expected")
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < 2 ** 64:
+            raise ValueError(f"shuffled: seed {seed} outside 0 .. 2^64 - 1")
+        raw = _ffi.DeviceBuffer(max(self.n, 16))
+        borders = None
+        try:
+            stats = (_ffi.i64 * 2)()
+            check(_ffi.lib().kmap_shuffle_packed_dev(self.codes.ptr, self.inval_orig.ptr, self.n, int(klet), int(seed), raw.ptr, stats, None))
+            borders = _ffi.DeviceBuffer(max(self.n_seq, 1) * 16)
+            if self.n_seq:
+                check(_ffi.lib().kmap_memcpy_d2d(borders.ptr, self.borders.ptr, self.n_seq * 16, None))
+            out = DeviceSeq.from_device(raw, self.n, borders, self.n_seq)
+        except BaseException:
+            # no DeviceSeq owns the two buffers unless from_device returned.  It frees raw itself once packed and never borders;
+            # DeviceBuffer.free is a no-op the second time, so freeing both here is right wherever the failure came from.
+            raw.free()
+            if borders is not None:
+                borders.free()
+            raise
+        out.borders_host = None if self.borders_host is None else self.borders_host.copy()
+        out.read_len = None if self.read_len is None else self.read_len.copy()
+        out.out_read_len = out.read_len
+        out.shuffle_stats = (int(stats[0]), int(stats[1]))
+        return out
+
     def _lazy_release(self, h):
         with self._lazy_lock:
             if self._lazy_all is not None:
