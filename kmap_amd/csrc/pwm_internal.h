@@ -1,7 +1,15 @@
-// pwm_internal.h -- the device side shared by pwm_scan.hip (scan_pwm) and pwm_refine.hip (refine_pwm): the chunk tables, the group
-// loads, the window helpers and pass A (hit bit per position + hit count per wave tile); DESIGN.md sections 11 and 13
+// pwm_internal.h -- what pwm_scan.hip (scan_pwm), pwm_refine.hip (refine_pwm) and pwm_readscore.hip (evaluate_pwm) share; DESIGN.md
+// sections 11, 13 and 14.
+//   device: the chunk tables, the group loads, the window helpers, pass A (pwm_hits_kernel: hit bit per position + hit count per wave
+//           tile) and for_each_hit, the ONE sparse traversal of pass A's hits that every later pass of scan and refine is a call of
+//   host:   PwmPlan (an entry point's checks, the weights as a kernel argument, the launch geometry), pwm_pass_a (scratch, launch,
+//           exclusive scan of the tile counts, total) and with_bool (a run-time flag as a template argument)
 #pragma once
+#include <algorithm>
+#include <type_traits>
+
 #include "common.h"
+#include "scan_util.h"
 
 namespace {
 
@@ -113,6 +121,122 @@ __global__ __launch_bounds__(PW_TPB) void pwm_hits_kernel(const uint32_t *__rest
         for (int o = 32; o; o >>= 1) cnt += __shfl_down(cnt, o);
         if (lane == 0) tile_cnt[t] = cnt;
     }
+}
+
+// the read of array position p: the last one that starts at or before it (a valid window cannot cross the 255 behind a read)
+__device__ __forceinline__ int64_t find_read(const int64_t *__restrict__ borders, int64_t n_seq, int64_t p) {
+    int64_t lo = 0, hi = n_seq;            // borders[2 lo] <= p (or lo == 0), borders[2 hi] > p (or hi == n_seq)
+    while (hi - lo > 1) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (borders[2 * mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// The sparse traversal of pass A's hits, in array order per lane: the block's waves stride over the tiles with hits, a lane takes the
+// hit bits of its group, scores each hit again and hands it to on_hit(i, p, r, start, v, fwd, rc): window i of the group, array
+// position p, read r that starts at `start`, the window's bits (win_bits) and its scores (rc only with RC).
+//   on_tile(t, bits, lane)  the whole wave, once per tile with hits, before its hits are visited: the place for wave-wide shuffles
+//   READS                   the callbacks need the hit's read.  A binary search of the borders places the lane's first hit, the
+//                           following ones step forward (hits ascend).  on_read(left, entered) follows the lane from read to read:
+//                           (-1, r) in front of its first hit, (r, r + 1) for every border it steps over, (r, -1) behind its last
+//                           hit.  What a caller gathers per read it hands in at `left` and starts anew, so at (-1, r) it holds
+//                           nothing.  Without READS the borders are never touched, r = start = 0 and on_read is not called.
+template <bool RC, bool READS, class OnTile, class OnHit, class OnRead>
+__device__ __forceinline__ void for_each_hit(const int2 *tab, const uint32_t *__restrict__ codes, const uint16_t *__restrict__ inval,
+                                             int64_t n_data, int64_t n_tiles, int nch, const uint16_t *__restrict__ hit16,
+                                             const uint32_t *__restrict__ tile_cnt, const int64_t *__restrict__ borders, int64_t n_seq,
+                                             OnTile on_tile, OnHit on_hit, OnRead on_read) {
+    const int lane = threadIdx.x & (KMAP_WAVE - 1), wave = threadIdx.x >> 6;
+    for (int64_t t = (int64_t)blockIdx.x * PW_WAVES + wave; t < n_tiles; t += (int64_t)gridDim.x * PW_WAVES) {
+        if (tile_cnt[t] == 0) continue;    // uniform
+        const int64_t g = t * PW_TILE_GROUPS + lane;
+        const Grp w = load_grp(codes, inval, g, n_data, lane);
+        uint32_t bits = g < n_data ? (uint32_t)hit16[g] : 0u;
+        on_tile(t, bits, lane);
+        if (bits) {        // (no `continue`: the wave meets again at the next tile's shuffles)
+            int64_t r = 0, start = 0;
+            if (READS) {
+                r = find_read(borders, n_seq, g * 16 + (__builtin_clz(bits) - 16));
+                start = borders[2 * r];
+                on_read((int64_t)-1, r);
+            }
+            while (bits) {
+                const int i = __builtin_clz(bits) - 16;
+                bits &= ~(0x8000u >> i);
+                const int64_t p = g * 16 + i;
+                while (READS && r + 1 < n_seq) {       // hits ascend: step to the hit's read
+                    const int64_t nx = borders[2 * (r + 1)];
+                    if (nx > p) break;
+                    on_read(r, r + 1);
+                    ++r;
+                    start = nx;
+                }
+                const uint64_t v = win_bits(w, i);
+                int fwd, rc;
+                win_score<RC>(tab, v, nch, fwd, rc);
+                on_hit(i, p, r, start, v, fwd, rc);
+            }
+            if (READS) on_read(r, (int64_t)-1);
+        }
+    }
+}
+template <bool RC, bool READS, class OnHit, class OnRead>
+__device__ __forceinline__ void for_each_hit(const int2 *tab, const uint32_t *__restrict__ codes, const uint16_t *__restrict__ inval,
+                                             int64_t n_data, int64_t n_tiles, int nch, const uint16_t *__restrict__ hit16,
+                                             const uint32_t *__restrict__ tile_cnt, const int64_t *__restrict__ borders, int64_t n_seq,
+                                             OnHit on_hit, OnRead on_read) {
+    for_each_hit<RC, READS>(tab, codes, inval, n_data, n_tiles, nch, hit16, tile_cnt, borders, n_seq, [](int64_t, uint32_t, int) {},
+                            on_hit, on_read);
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------
+
+// f(std::true_type) or f(std::false_type): a run-time flag as a template argument, `decltype(flag)::value` inside a generic lambda
+template <class F>
+inline void with_bool(bool b, F f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+struct PwmPlan {
+    PwmWeights wt;
+    int width, nch;
+    int64_t n_data, n_tiles;   // groups of 16 positions; wave tiles of 64 groups
+    unsigned grid;             // 0 when n == 0
+};
+// the checks of a PWM entry point (`who` = its prefix in the messages), the weights and the geometry of n positions
+inline int pwm_plan(PwmPlan &pl, const char *who, int64_t n, int64_t n_seq, int width, const int32_t *weights) {
+    KMAP_REQUIRE(width >= 4 && width <= 31, "%s: width=%d outside 4..31", who, width);
+    KMAP_REQUIRE(weights, "%s: null weights", who);
+    KMAP_REQUIRE(n >= 0 && n_seq >= 0, "%s: negative size", who);
+    memset(&pl.wt, 0, sizeof pl.wt);
+    for (int b = 0; b < 4; ++b)
+        for (int j = 0; j < width; ++j) pl.wt.w[b][j] = weights[b * width + j];
+    pl.width = width;
+    pl.nch = (width + 3) / 4;
+    pl.n_data = (n + 15) >> 4;
+    pl.n_tiles = (pl.n_data + PW_TILE_GROUPS - 1) / PW_TILE_GROUPS;
+    pl.grid = (unsigned)std::min<int64_t>((pl.n_tiles + PW_WAVES - 1) / PW_WAVES, PW_MAX_BLOCKS);
+    return KMAP_OK;
+}
+
+// pass A on `st` (n_tiles > 0): hit16[n_data], tile_cnt[n_tiles] and its exclusive scan tile_off[n_tiles + 1] in the scratch slots
+// HASH, B and PART; returns once *total = tile_off[n_tiles], the number of hits, has arrived
+inline int pwm_pass_a(const PwmPlan &pl, const uint32_t *codes, const uint16_t *inval, int32_t threshold, int revcom, hipStream_t st,
+                      uint16_t **hit16, uint32_t **tile_cnt, uint64_t **tile_off, uint64_t *total) {
+    KMAP_TRY(kmap_scratch((void **)hit16, (size_t)pl.n_data * 2, st, KMAP_SLOT_HASH));
+    KMAP_TRY(kmap_scratch((void **)tile_cnt, (size_t)pl.n_tiles * 4, st, KMAP_SLOT_B));
+    KMAP_TRY(kmap_scratch((void **)tile_off, ((size_t)pl.n_tiles + 1) * 8, st, KMAP_SLOT_PART));
+    with_bool(revcom, [&](auto rc) {
+        pwm_hits_kernel<decltype(rc)::value><<<pl.grid, PW_TPB, 0, st>>>(codes, inval, pl.n_data, pl.n_tiles, pl.wt, pl.width, pl.nch,
+                                                                         threshold, *hit16, *tile_cnt);
+    });
+    KMAP_CHECK_HIP(hipGetLastError());
+    KMAP_TRY(exclusive_scan_u32(*tile_cnt, pl.n_tiles, *tile_off, st));
+    *total = 0;
+    KMAP_CHECK_HIP(hipMemcpyAsync(total, *tile_off + pl.n_tiles, 8, hipMemcpyDeviceToHost, st));
+    KMAP_CHECK_HIP(hipStreamSynchronize(st));
+    return KMAP_OK;
 }
 
 }  // namespace

@@ -18,8 +18,6 @@
 //   * readscore_unpack_kernel: key -> score / loc / strand (INT32_MIN / -1 / 0 for a zero key) + the number of scorable reads.
 //   * readscore_hist_kernel<LDS>: uint64 histogram of the scorable reads' scores; block-private uint32 bins in LDS when the range
 //     fits (then one global integer atomic per non-zero bin and block), global integer atomics otherwise.  Order-free either way.
-#include <algorithm>
-
 #include "common.h"
 #include "pwm_internal.h"
 
@@ -190,9 +188,8 @@ extern "C" {
 int kmap_readscore_packed_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, const int64_t *borders_dev,
                               int64_t n_seq, int width, const int32_t *weights, int revcom, int32_t *score_dev, int32_t *loc_dev,
                               uint8_t *strand_dev, int64_t *n_scored, void *stream) {
-    KMAP_REQUIRE(width >= 4 && width <= 31, "readscore: width=%d outside 4..31", width);
-    KMAP_REQUIRE(weights, "readscore: null weights");
-    KMAP_REQUIRE(n >= 0 && n_seq >= 0, "readscore: negative size");
+    PwmPlan pl;
+    KMAP_TRY(pwm_plan(pl, "readscore", n, n_seq, width, weights));
     if (n_scored) *n_scored = 0;
     if (n_seq == 0) return KMAP_OK;
     KMAP_REQUIRE(score_dev && loc_dev && strand_dev, "readscore: null result pointer");
@@ -203,17 +200,10 @@ int kmap_readscore_packed_dev(const uint32_t *codes_dev, const uint16_t *inval_d
     KMAP_CHECK_HIP(hipMemsetAsync(acc, 0, ((size_t)n_seq + 2) * 8, st));
     if (n > 0) {
         KMAP_REQUIRE(codes_dev && inval_dev && borders_dev, "readscore: null pointer");
-        const int64_t n_data = (n + 15) >> 4, n_tiles = (n_data + PW_TILE_GROUPS - 1) / PW_TILE_GROUPS;
-        const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + PW_WAVES - 1) / PW_WAVES, PW_MAX_BLOCKS);
-        PwmWeights wt;
-        memset(&wt, 0, sizeof wt);
-        for (int b = 0; b < 4; ++b)
-            for (int j = 0; j < width; ++j) wt.w[b][j] = weights[b * width + j];
-        const int nch = (width + 3) / 4;
-        if (revcom)
-            readscore_kernel<true><<<grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, n_data, n_tiles, wt, width, nch, borders_dev, n_seq, key);
-        else
-            readscore_kernel<false><<<grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, n_data, n_tiles, wt, width, nch, borders_dev, n_seq, key);
+        with_bool(revcom, [&](auto rc) {
+            readscore_kernel<decltype(rc)::value><<<pl.grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, pl.n_data, pl.n_tiles, pl.wt, width, pl.nch,
+                                                                              borders_dev, n_seq, key);
+        });
         KMAP_CHECK_HIP(hipGetLastError());
     }
     readscore_unpack_kernel<<<grid_for(n_seq, 256), 256, 0, st>>>(key, n_seq, score_dev, loc_dev, strand_dev, acc);

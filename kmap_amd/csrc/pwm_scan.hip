@@ -10,18 +10,15 @@
 //   * lane = one group of 16 window starts; it needs the group's code word and the next two (16 + 30 positions) and takes those
 //     from the two lanes above it (the last two lanes of a wave load them: the halo groups make that legal for every data group).
 //   * pass A (pwm_hits_kernel): hit bit per position (uint16 per group, window i in bit 15 - i) + hit count per wave tile of 1024
-//     positions; exclusive scan of the tile counts; pass B (pwm_write_kernel): the tiles with hits evaluate their (sparse) hits
-//     again and write loc / score / strand at the tile's offset.  Array order IS read order, ascending inside a read, so the lists
-//     need no sort.  A hit's read is the last read that starts at or before it (a valid window cannot cross the 255 behind a read):
-//     binary search of the borders for a lane's first hit, a step forward for the following ones; the per-read counts are integer
-//     atomic adds of run lengths (order-free, so the result is deterministic).  Nothing depends on the reads' lengths: empty reads,
-//     a read that spans thousands of tiles, more than 65 535 reads and any number of hits per read take the same path.
-#include <algorithm>
-
+//     positions; exclusive scan of the tile counts (pwm_pass_a, pwm_internal.h); pass B (pwm_write_kernel): the sparse traversal
+//     of pwm_internal.h (for_each_hit: the tiles with hits evaluate their hits again, each with the read it lies in) writes loc /
+//     score / strand at the tile's offset.  Array order IS read order, ascending inside a read, so the lists need no sort.  The
+//     per-read counts are integer atomic adds of run lengths (order-free, so the result is deterministic).  Nothing depends on the
+//     reads' lengths: empty reads, a read that spans thousands of tiles, more than 65 535 reads and any number of hits per read
+//     take the same path.
 #include "common.h"
 #include "pwm_internal.h"
 #include "scan_internal.h"
-#include "scan_util.h"
 
 namespace {
 
@@ -36,53 +33,31 @@ __global__ __launch_bounds__(PW_TPB) void pwm_write_kernel(const uint32_t *__res
     __shared__ int2 tab[PW_MAX_CHUNKS * 256];
     __shared__ int32_t wl[128];
     build_table(tab, wl, wt, width, nch);
-    const int lane = threadIdx.x & (KMAP_WAVE - 1), wave = threadIdx.x >> 6;
-    for (int64_t t = (int64_t)blockIdx.x * PW_WAVES + wave; t < n_tiles; t += (int64_t)gridDim.x * PW_WAVES) {
-        if (tile_cnt[t] == 0) continue;    // uniform
-        const int64_t g = t * PW_TILE_GROUPS + lane;
-        const Grp w = load_grp(codes, inval, g, n_data, lane);
-        uint32_t bits = g < n_data ? (uint32_t)hit16[g] : 0u;
-        const uint32_t cnt = (uint32_t)__builtin_popcount(bits);
-        uint32_t inc = cnt;
-        for (int o = 1; o < KMAP_WAVE; o <<= 1) {
-            const uint32_t u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
-        if (bits) {        // (no `continue`: the wave meets again at the next tile's shuffles)
-            uint64_t out = tile_off[t] + (inc - cnt);
-            // the read of the lane's first hit: the last one that starts at or before it
-            int64_t p = g * 16 + (__builtin_clz(bits) - 16);
-            int64_t lo = 0, hi = n_seq;        // borders[2 lo] <= p (or lo == 0), borders[2 hi] > p (or hi == n_seq)
-            while (hi - lo > 1) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if (borders[2 * mid] <= p) lo = mid; else hi = mid;
+    uint64_t out = 0;      // where the lane's next hit goes
+    int32_t run = 0;       // the lane's hits in the read it is in
+    for_each_hit<RC, true>(
+        tab, codes, inval, n_data, n_tiles, nch, hit16, tile_cnt, borders, n_seq,
+        [&](int64_t t, uint32_t bits, int lane) {      // wave-uniform: the lanes' offsets inside the tile, before any hit is visited
+            const uint32_t cnt = (uint32_t)__builtin_popcount(bits);
+            uint32_t inc = cnt;
+            for (int o = 1; o < KMAP_WAVE; o <<= 1) {
+                const uint32_t u = __shfl_up(inc, o);
+                if (lane >= o) inc += u;
             }
-            int64_t r = lo, start = borders[2 * r];
-            int32_t run = 0;
-            while (bits) {
-                const int i = __builtin_clz(bits) - 16;
-                bits &= ~(0x8000u >> i);
-                p = g * 16 + i;
-                while (r + 1 < n_seq) {        // hits ascend: step to the hit's read, counting what the last one got
-                    const int64_t nx = borders[2 * (r + 1)];
-                    if (nx > p) break;
-                    if (run) atomicAdd(&hits[r], run);
-                    run = 0;
-                    ++r;
-                    start = nx;
-                }
-                int fwd, rc;
-                win_score<RC>(tab, win_bits(w, i), nch, fwd, rc);
-                const bool minus = RC && rc > fwd;
-                pos[out] = (int32_t)(p - start);
-                score[out] = minus ? rc : fwd;
-                strand[out] = minus ? 1 : 0;
-                ++out;
-                ++run;
-            }
-            if (run) atomicAdd(&hits[r], run);
-        }
-    }
+            out = tile_off[t] + (inc - cnt);
+        },
+        [&](int, int64_t p, int64_t, int64_t start, uint64_t, int fwd, int rc) {
+            const bool minus = RC && rc > fwd;
+            pos[out] = (int32_t)(p - start);
+            score[out] = minus ? rc : fwd;
+            strand[out] = minus ? 1 : 0;
+            ++out;
+            ++run;
+        },
+        [&](int64_t left, int64_t) {                   // counting what the read the lane leaves got
+            if (run) atomicAdd(&hits[left], run);
+            run = 0;
+        });
 }
 
 int reserve_scores(kmap_scan *s, uint64_t total) {
@@ -106,9 +81,8 @@ int kmap_pwm_scan_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint
                              int64_t n_seq, int width, const int32_t *weights, int32_t threshold, int revcom, int64_t *total_hits,
                              void *stream) {
     KMAP_REQUIRE(s, "pwm_scan: null handle");
-    KMAP_REQUIRE(width >= 4 && width <= 31, "pwm_scan: width=%d outside 4..31", width);
-    KMAP_REQUIRE(weights, "pwm_scan: null weights");
-    KMAP_REQUIRE(n >= 0 && n_seq >= 0, "pwm_scan: negative size");
+    PwmPlan pl;
+    KMAP_TRY(pwm_plan(pl, "pwm_scan", n, n_seq, width, weights));
     s->n_seq = n_seq;
     s->total = 0;
     s->pwm = 1;
@@ -118,38 +92,20 @@ int kmap_pwm_scan_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint
     hipStream_t st = as_stream(stream);
     KMAP_TRY(kmap_scan_reserve(s, n_seq));
     KMAP_CHECK_HIP(hipMemsetAsync(s->hits, 0, (size_t)n_seq * 4, st));
-    const int64_t n_data = (n + 15) >> 4, n_tiles = (n_data + PW_TILE_GROUPS - 1) / PW_TILE_GROUPS;
-    if (n_tiles == 0) return KMAP_OK;
-    PwmWeights wt;
-    memset(&wt, 0, sizeof wt);
-    for (int b = 0; b < 4; ++b)
-        for (int j = 0; j < width; ++j) wt.w[b][j] = weights[b * width + j];
-    const int nch = (width + 3) / 4;
+    if (pl.n_tiles == 0) return KMAP_OK;
     uint16_t *hit16 = nullptr;
     uint32_t *tile_cnt = nullptr;
     uint64_t *tile_off = nullptr;
-    KMAP_TRY(kmap_scratch((void **)&hit16, (size_t)n_data * 2, st, KMAP_SLOT_HASH));
-    KMAP_TRY(kmap_scratch((void **)&tile_cnt, (size_t)n_tiles * 4, st, KMAP_SLOT_B));
-    KMAP_TRY(kmap_scratch((void **)&tile_off, ((size_t)n_tiles + 1) * 8, st, KMAP_SLOT_PART));
-    const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + PW_WAVES - 1) / PW_WAVES, PW_MAX_BLOCKS);
-    if (revcom)
-        pwm_hits_kernel<true><<<grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, n_data, n_tiles, wt, width, nch, threshold, hit16, tile_cnt);
-    else
-        pwm_hits_kernel<false><<<grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, n_data, n_tiles, wt, width, nch, threshold, hit16, tile_cnt);
-    KMAP_CHECK_HIP(hipGetLastError());
-    KMAP_TRY(exclusive_scan_u32(tile_cnt, n_tiles, tile_off, st));
     uint64_t total = 0;
-    KMAP_CHECK_HIP(hipMemcpyAsync(&total, tile_off + n_tiles, 8, hipMemcpyDeviceToHost, st));
-    KMAP_CHECK_HIP(hipStreamSynchronize(st));
+    KMAP_TRY(pwm_pass_a(pl, codes_dev, inval_dev, threshold, revcom, st, &hit16, &tile_cnt, &tile_off, &total));
     KMAP_TRY(kmap_scan_reserve_pos(s, total));
     KMAP_TRY(reserve_scores(s, total));
     if (total) {
-        if (revcom)
-            pwm_write_kernel<true><<<grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, n_data, n_tiles, wt, width, nch, hit16, tile_cnt, tile_off,
-                                                           borders_dev, n_seq, s->hits, s->pos, s->score, s->strand);
-        else
-            pwm_write_kernel<false><<<grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, n_data, n_tiles, wt, width, nch, hit16, tile_cnt, tile_off,
-                                                            borders_dev, n_seq, s->hits, s->pos, s->score, s->strand);
+        with_bool(revcom, [&](auto rc) {
+            pwm_write_kernel<decltype(rc)::value><<<pl.grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, pl.n_data, pl.n_tiles, pl.wt, width,
+                                                                              pl.nch, hit16, tile_cnt, tile_off, borders_dev, n_seq,
+                                                                              s->hits, s->pos, s->score, s->strand);
+        });
         KMAP_CHECK_HIP(hipGetLastError());
     }
     s->total = (int64_t)total;

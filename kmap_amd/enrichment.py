@@ -8,7 +8,6 @@ kernel of its own: the Hamming-ball mass of every consensus over both tables.  H
 rows and the file formats; the join, the scores and the selection have no CPU path."""
 import ctypes as C
 import math
-import os
 from pathlib import Path
 
 import numpy as np
@@ -156,19 +155,11 @@ def _enrich_kmers(res_dir, control_fasta_file, kmer_len=(), top_n=1000, min_coun
     per --kmer_len, enrichment_info.csv and (with a consensus file) motif_enrichment.csv in output_dir (default
     res_dir/kmer_enrichment).  Every argument and file is checked before the device is touched or anything is written.  Under a
     torch.distributed launch rank 0 works alone.  Returns {"kmers": {k: (idx, kh, a, b, z)}, "info": [...], "motifs": [...]}."""
-    from . import _policy
-    from ._toml import load_toml
-    from .kmer_count import DeviceCounts, FileNameDict, encode_fasta, gen_motif_def_dict, hash2kmer, kmer2hash, load_array_pickle
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and int(os.environ.get("RANK", "0")) != 0:
+    from .kmer_count import (DeviceCounts, FileNameDict, encode_fasta, gen_motif_def_dict, hash2kmer, kmer2hash, load_array_pickle,
+                             load_config, rank0_only, result_paths)
+    if not rank0_only():
         return None
-    res = Path(res_dir)
-    cfg_path = res / FileNameDict["config_file"]
-    if not cfg_path.exists():
-        raise ValueError(f"{cfg_path} is missing: not a result directory of preproc")
-    seq_path, border_path = res / FileNameDict["processed_fasta_file"], res / FileNameDict["processed_fasta_seqboarder_file"]
-    for p in (seq_path, border_path):
-        if not p.exists():
-            raise ValueError(f"{p} is missing: not a result directory of preproc")
+    res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
     if control_fasta_file is None or not Path(control_fasta_file).is_file():
         raise ValueError(f"control FASTA file {control_fasta_file} is missing")
     kmer_lens = []
@@ -199,9 +190,7 @@ def _enrich_kmers(res_dir, control_fasta_file, kmer_len=(), top_n=1000, min_coun
                 raise ValueError(f"{conseq_path}: consensus {c!r} has letters other than A, C, G, T")
     if not kmer_lens and not conseqs:
         raise ValueError("enrich_kmers: nothing to do: no --kmer_len given and no consensus file found")
-    cfg = load_toml(cfg_path)
-    _policy.apply_config(cfg)
-    revcom = bool(cfg["kmer_count"]["revcom_mode"])
+    cfg, revcom = load_config(cfg_path)
     dedupe = not bool(cfg["general"]["repetitive_mode"])
     motif_def = gen_motif_def_dict(cfg) if conseqs else {}
     by_len = {}

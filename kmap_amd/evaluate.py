@@ -7,13 +7,12 @@ z with the tie correction) and the pooled two-proportion z of enrichment.py at e
 bit), so everything behind the kernel is exact integer arithmetic on two histograms: no sort, no tolerance, two runs write the same
 bytes.  Host code here is that arithmetic, argument checking and the file formats; the scoring has no CPU path."""
 import math
-import os
 from pathlib import Path
 
 import numpy as np
 
 from .enrichment import enrich_z, log2_fold
-from .pwm import SCORE_UNIT, min_score_threshold, pwm_consensus, pwm_threshold, pwm_weights, read_count_matrix
+from .pwm import SCORE_UNIT, load_matrices
 
 EVAL_FILE, HIST_FILE, READS_FILE = "pwm_eval.csv", "score_hist_motif{i}_{consensus}.csv", "read_scores_motif{i}_{consensus}.tsv"
 OUTPUT_DIR = "pwm_eval"
@@ -141,19 +140,10 @@ def _evaluate_pwm(res_dir, control_fasta_file, matrix_files, p_value=1e-4, min_s
     (default res_dir/pwm_eval).  Every matrix is read, its thresholds found and every ValueError raised before the device is touched
     or a file is written.  Under a torch.distributed launch rank 0 works alone.  Returns one dict per matrix: evaluate_histograms'
     fields plus Hf, Hc, lo, fg_unscorable, control_unscorable."""
-    from . import _policy
-    from ._toml import load_toml
-    from .kmer_count import FileNameDict, encode_fasta, load_array_pickle
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and int(os.environ.get("RANK", "0")) != 0:
+    from .kmer_count import encode_fasta, load_array_pickle, load_config, rank0_only, result_paths
+    if not rank0_only():
         return None
-    res = Path(res_dir)
-    cfg_path = res / FileNameDict["config_file"]
-    if not cfg_path.exists():
-        raise ValueError(f"{cfg_path} is missing: not a result directory of preproc")
-    seq_path, border_path = res / FileNameDict["processed_fasta_file"], res / FileNameDict["processed_fasta_seqboarder_file"]
-    for p in (seq_path, border_path):
-        if not p.exists():
-            raise ValueError(f"{p} is missing: not a result directory of preproc")
+    res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
     if control_fasta_file is None or not Path(control_fasta_file).is_file():
         raise ValueError(f"control FASTA file {control_fasta_file} is missing")
     matrix_files = [str(f) for f in matrix_files]
@@ -161,22 +151,12 @@ def _evaluate_pwm(res_dir, control_fasta_file, matrix_files, p_value=1e-4, min_s
         raise ValueError("evaluate_pwm: no matrix file given")
     if int(min_reads) != min_reads or min_reads < 1:
         raise ValueError(f"min_reads {min_reads} < 1")
-    cfg = load_toml(cfg_path)
-    _policy.apply_config(cfg)
-    revcom = bool(cfg["kmer_count"]["revcom_mode"]) if revcom_mode is None else bool(revcom_mode)
-    motifs = []
-    for f in matrix_files:
-        C = read_count_matrix(f)
-        try:
-            W = pwm_weights(C, pseudocount)
-            t, lo, hi = pwm_threshold(W, p_value)
-            if hi - lo + 1 > MAX_BINS:
-                raise ValueError(f"scores from {lo} to {hi}: more than 2^22 different scores are not supported")
-        except ValueError as exc:
-            raise ValueError(f"{f}: {exc}") from None
-        if min_score is not None:
-            t = min_score_threshold(min_score)
-        motifs.append((f, C, W, pwm_consensus(C), t, lo, hi))
+    _, revcom = load_config(cfg_path, revcom_mode)
+
+    def check_bins(lo, hi):
+        if hi - lo + 1 > MAX_BINS:
+            raise ValueError(f"scores from {lo} to {hi}: more than 2^22 different scores are not supported")
+    motifs = load_matrices(matrix_files, pseudocount, p_value, min_score, check_bins)
 
     from .motif_discovery import DeviceSeq
     fg_seq = DeviceSeq(load_array_pickle(seq_path), load_array_pickle(border_path))

@@ -9,6 +9,7 @@ Python like the reference's.
 """
 import ctypes as C
 import gzip
+import os
 import pickle
 from dataclasses import dataclass, fields
 from importlib.resources import files
@@ -49,6 +50,33 @@ FileNameDict = {
     "ld_data_file": "low_dim_data.tsv",
     "ld_fig_file_stem": "ld_data",
 }
+
+
+# ---- the prologue of the verbs that work on a result directory with one GPU ---------------------------------------------------
+def rank0_only():
+    """False on every rank but 0 of a torch.distributed launch: rank 0 works alone, the others return at once"""
+    return int(os.environ.get("WORLD_SIZE", "1")) <= 1 or int(os.environ.get("RANK", "0")) == 0
+
+
+def result_paths(res_dir, config=True, reads=False, made_by="preproc"):
+    """(res_dir as a Path, then the paths asked for: config.toml; the encoded reads and their borders), each checked to exist:
+    a ValueError before anything is loaded"""
+    res = Path(res_dir)
+    names = ["config_file"] * bool(config) + ["processed_fasta_file", "processed_fasta_seqboarder_file"] * bool(reads)
+    paths = [res / FileNameDict[name] for name in names]
+    for p in paths:
+        if not p.exists():
+            raise ValueError(f"{p} is missing: not a result directory of {made_by}")
+    return (res, *paths)
+
+
+def load_config(cfg_path, revcom_mode=None):
+    """(the run's config.toml, applied to the process; revcom_mode, the config's own unless given)"""
+    from . import _policy
+    from ._toml import load_toml
+    cfg = load_toml(cfg_path)
+    _policy.apply_config(cfg)
+    return cfg, bool(cfg["kmer_count"]["revcom_mode"]) if revcom_mode is None else bool(revcom_mode)
 
 MISSING_VAL = 255
 _BASES = "ACGT"

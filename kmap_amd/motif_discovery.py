@@ -70,6 +70,20 @@ def write_lines(str_list: List, outfile):
 
 
 # ---- device-resident sequence array ----------------------------------------------------------------
+def _as_weights(W, who):
+    """a weight matrix as the C ABI takes it: contiguous int32 [4, width]"""
+    W = np.ascontiguousarray(W, dtype=np.int32)
+    if W.ndim != 2 or W.shape[0] != 4:
+        raise ValueError(f"{who}: weights of shape {W.shape}, expected (4, width) with rows A, C, G, T")
+    return W
+
+
+def _as_threshold(t, who):
+    if not -2 ** 31 <= int(t) < 2 ** 31:
+        raise ValueError(f"{who}: threshold {t} does not fit int32")
+    return int(t)
+
+
 class DeviceSeq:
     """The encoded reads resident in HBM as 2-bit codes + invalid bitmask (packed.hip), plus the (n_seq, 2) borders.
     `inval_orig` is the pristine mask, `inval_work` the one find_motif masks; the codes are shared."""
@@ -181,16 +195,32 @@ class DeviceSeq:
         check(_ffi.lib().kmap_scan_declare_uniform(handle, self.borders.ptr, self.n_seq, lay[0], lay[1], C.byref(ok), None))
         return bool(ok.value)
 
+    def _new_scan_handle(self):
+        h = _ffi.vp()
+        check(_ffi.lib().kmap_scan_create(C.byref(h)))
+        self.declare_layout(h.value)
+        return h.value
+
+    def _own_scan_handle(self):
+        """the handle of scan() and scan_pwm(), created on first use"""
+        if self._scan is None:
+            self._scan = self._new_scan_handle()
+        return self._scan
+
+    def _take_lazy_handle(self):
+        """a free handle of the lazy rotation, or a new one; it goes back through _lazy_release"""
+        with self._lazy_lock:
+            h = self._lazy_free.pop() if self._lazy_free else None
+        if h is None:
+            h = self._new_scan_handle()
+            self._lazy_all.append(h)
+        return h
+
     def scan(self, k, consensus_kh, radius, revcom):
         """positions at each read's minimum hit distance (original, unmasked reads):
         returns (hits_per_read int32[n_seq], positions int32[total])."""
-        if self._scan is None:
-            h = _ffi.vp()
-            check(_ffi.lib().kmap_scan_create(C.byref(h)))
-            self._scan = h.value
-            self.declare_layout(self._scan)
         tot = _ffi.i64(0)
-        check(_ffi.lib().kmap_scan_run_packed_dev(self._scan, self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr,
+        check(_ffi.lib().kmap_scan_run_packed_dev(self._own_scan_handle(), self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr,
                                                   self.n_seq, k, int(consensus_kh), int(radius), int(revcom), C.byref(tot),
                                                   self.planes.ptr, None))
         hits = np.empty(self.n_seq, np.int32)
@@ -203,14 +233,7 @@ class DeviceSeq:
         .max_hits` are known at once (what scan_motif's candidate table needs), the two arrays are fetched on first use -- by the
         background CSV writer in scan_motif, off the critical path.  Handles rotate: a fetched (or dropped) ScanHits hands its
         handle back, so a run allocates a handful of result buffers once instead of one set per consensus."""
-        with self._lazy_lock:
-            h = self._lazy_free.pop() if self._lazy_free else None
-        if h is None:
-            hv = _ffi.vp()
-            check(_ffi.lib().kmap_scan_create(C.byref(hv)))
-            h = hv.value
-            self.declare_layout(h)
-            self._lazy_all.append(h)
+        h = self._take_lazy_handle()
         tot, nhit, mx = _ffi.i64(0), _ffi.i64(0), _ffi.i32(0)
         check(_ffi.lib().kmap_scan_run_packed_dev(h, self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr,
                                                   self.n_seq, k, int(consensus_kh), int(radius), int(revcom), C.byref(tot),
@@ -219,26 +242,17 @@ class DeviceSeq:
         return ScanHits(self, h, self.n_seq, tot.value, nhit.value, mx.value)
 
     def _pwm_run(self, h, W, t, revcom):
-        W = np.ascontiguousarray(W, dtype=np.int32)
-        if W.ndim != 2 or W.shape[0] != 4:
-            raise ValueError(f"scan_pwm: weights of shape {W.shape}, expected (4, width) with rows A, C, G, T")
-        if not -2 ** 31 <= int(t) < 2 ** 31:
-            raise ValueError(f"scan_pwm: threshold {t} does not fit int32")
+        W, t = _as_weights(W, "scan_pwm"), _as_threshold(t, "scan_pwm")
         tot = _ffi.i64(0)
         check(_ffi.lib().kmap_pwm_scan_packed_dev(h, self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq,
-                                                  W.shape[1], ptr(W), int(t), int(bool(revcom)), C.byref(tot), None))
+                                                  W.shape[1], ptr(W), t, int(bool(revcom)), C.byref(tot), None))
         return tot.value
 
     def scan_pwm(self, W, t, revcom):
         """every window of the original reads whose weight-matrix score (W: int32 [4, width], rows A C G T; with revcom the larger
         of the two strands' scores) is >= t and that touches no invalid position (csrc/pwm_scan.hip):
         returns (hits_per_read int32[n_seq], positions int32[total], scores int32[total], strand uint8[total]: 0 '+', 1 '-')."""
-        if self._scan is None:
-            h = _ffi.vp()
-            check(_ffi.lib().kmap_scan_create(C.byref(h)))
-            self._scan = h.value
-            self.declare_layout(self._scan)
-        total = self._pwm_run(self._scan, W, t, revcom)
+        total = self._pwm_run(self._own_scan_handle(), W, t, revcom)
         hits, pos = np.empty(self.n_seq, np.int32), np.empty(total, np.int32)
         scores, strand = np.empty(total, np.int32), np.empty(total, np.uint8)
         check(_ffi.lib().kmap_pwm_scan_fetch(self._scan, ptr(hits), ptr(pos), ptr(scores), ptr(strand)))
@@ -246,14 +260,7 @@ class DeviceSeq:
 
     def scan_pwm_lazy(self, W, t, revcom):
         """scan_pwm() whose (hits_per_read, positions) stay in HBM like scan_lazy()'s: a ScanHits (scores and strands are not kept)"""
-        with self._lazy_lock:
-            h = self._lazy_free.pop() if self._lazy_free else None
-        if h is None:
-            hv = _ffi.vp()
-            check(_ffi.lib().kmap_scan_create(C.byref(hv)))
-            h = hv.value
-            self.declare_layout(h)
-            self._lazy_all.append(h)
+        h = self._take_lazy_handle()
         nhit, mx = _ffi.i64(0), _ffi.i32(0)
         try:
             total = self._pwm_run(h, W, t, revcom)
@@ -267,15 +274,11 @@ class DeviceSeq:
         """one refinement step (csrc/pwm_refine.hip): of scan_pwm(W, t, revcom)'s hits on the original reads,
         every one (select_best False) or per read the one with the largest score, the smallest loc on a tie; returns
         (C' int64[4, width]: C'[b][j] = selected windows whose oriented base j is b, n_hits, n_selected, n_minus).  Needs no scan handle."""
-        W = np.ascontiguousarray(W, dtype=np.int32)
-        if W.ndim != 2 or W.shape[0] != 4:
-            raise ValueError(f"pwm_counts: weights of shape {W.shape}, expected (4, width) with rows A, C, G, T")
-        if not -2 ** 31 <= int(t) < 2 ** 31:
-            raise ValueError(f"pwm_counts: threshold {t} does not fit int32")
+        W, t = _as_weights(W, "pwm_counts"), _as_threshold(t, "pwm_counts")
         counts = np.zeros((4, W.shape[1]), np.int64)
         n_hits, n_sel, n_minus = _ffi.i64(0), _ffi.i64(0), _ffi.i64(0)
         check(_ffi.lib().kmap_refine_counts_packed_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq,
-                                                       W.shape[1], ptr(W), int(t), int(bool(revcom)), int(bool(select_best)), ptr(counts),
+                                                       W.shape[1], ptr(W), t, int(bool(revcom)), int(bool(select_best)), ptr(counts),
                                                        C.byref(n_hits), C.byref(n_sel), C.byref(n_minus), None))
         return counts, n_hits.value, n_sel.value, n_minus.value
 
@@ -283,9 +286,7 @@ class DeviceSeq:
         """per read the valid window with the largest score, on a tie the smallest loc (csrc/pwm_readscore.hip, DESIGN.md section
         14; scores and strands are scan_pwm's, there is no threshold): a ReadScores whose three arrays stay in HBM until fetch().
         Needs no scan handle."""
-        W = np.ascontiguousarray(W, dtype=np.int32)
-        if W.ndim != 2 or W.shape[0] != 4:
-            raise ValueError(f"read_scores: weights of shape {W.shape}, expected (4, width) with rows A, C, G, T")
+        W = _as_weights(W, "read_scores")
         out = ReadScores(self.n_seq)
         try:
             n_scored = _ffi.i64(0)
@@ -391,24 +392,28 @@ class ScanHits:
         self._host = None
         self._lock = threading.Lock()
 
+    def _fetch(self, fetch, hits_dtype):
+        """(hits, positions) on a private stream; the handle goes back to its sequence.  The caller holds the lock."""
+        if self._owner._lazy_all is None:
+            raise RuntimeError("ScanHits: the DeviceSeq was closed before the hit list was fetched")
+        hits, pos = np.empty(self.n_seq, hits_dtype), np.empty(self.total, np.int32)
+        check(_ffi.lib().kmap_set_device(self._owner.device))  # this may be a CSV writer thread (fresh threads start on device 0)
+        st = _ffi.vp()
+        check(_ffi.lib().kmap_stream_create(C.byref(st)))      # own stream: neither waits for nor blocks the launching thread
+        try:
+            check(fetch(self._handle, ptr(hits), ptr(pos), st.value))
+        finally:
+            _ffi.lib().kmap_stream_destroy(st.value)
+        self._owner._lazy_release(self._handle)
+        self._owner, self._handle = None, None
+        return hits, pos
+
     def host(self):
         with self._lock:
             if self._host is None:
                 if self._handle is None:
                     raise RuntimeError("ScanHits: the list was already handed to a CSV writer (host_u8)")
-                if self._owner._lazy_all is None:
-                    raise RuntimeError("ScanHits: the DeviceSeq was closed before the hit list was fetched")
-                hits, pos = np.empty(self.n_seq, np.int32), np.empty(self.total, np.int32)
-                check(_ffi.lib().kmap_set_device(self._owner.device))  # this may be a CSV writer thread (fresh threads start on device 0)
-                st = _ffi.vp()
-                check(_ffi.lib().kmap_stream_create(C.byref(st)))      # own stream: neither waits for nor blocks the launching thread
-                try:
-                    check(_ffi.lib().kmap_scan_fetch_stream(self._handle, ptr(hits), ptr(pos), st.value))
-                finally:
-                    _ffi.lib().kmap_stream_destroy(st.value)
-                self._owner._lazy_release(self._handle)
-                self._owner, self._handle = None, None
-                self._host = [hits, pos]
+                self._host = list(self._fetch(_ffi.lib().kmap_scan_fetch_stream, np.int32))
             return self._host
 
     @property
@@ -420,19 +425,7 @@ class ScanHits:
         back to its sequence, so this is the list's last use"""
         with self._lock:
             assert self._host is None and self._handle is not None and self.max_hits <= 255
-            if self._owner._lazy_all is None:
-                raise RuntimeError("ScanHits: the DeviceSeq was closed before the hit list was fetched")
-            hits, pos = np.empty(self.n_seq, np.uint8), np.empty(self.total, np.int32)
-            check(_ffi.lib().kmap_set_device(self._owner.device))
-            st = _ffi.vp()
-            check(_ffi.lib().kmap_stream_create(C.byref(st)))
-            try:
-                check(_ffi.lib().kmap_scan_fetch_stream_u8(self._handle, ptr(hits), ptr(pos), st.value))
-            finally:
-                _ffi.lib().kmap_stream_destroy(st.value)
-            self._owner._lazy_release(self._handle)
-            self._owner, self._handle = None, None
-            return hits, pos
+            return self._fetch(_ffi.lib().kmap_scan_fetch_stream_u8, np.uint8)
 
     def __del__(self):
         try:

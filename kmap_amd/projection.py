@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import check
-from .kmer_count import FileNameDict, get_hash_dtype
+from .kmer_count import FileNameDict, get_hash_dtype, load_config, rank0_only, result_paths
 from .visualization import dedupe_sums_rows, sigmoid, sums_rows_from_kmers
 
 MAX_NEIGHBOURS = 64               # csrc/project.hip PJ_MAX_NB: one lane per neighbour in the in-wave ordering
@@ -206,17 +206,10 @@ def read_anchors(res_dir, n_expected, labels_expected):
 def _project_kmers(res_dir, kmer_file, output_file=None, n_iter=100):
     """`kmap project_kmers`: config.toml + sample_kmers.pkl + low_dim_data.tsv + a file of k-mers -> projected_kmers.tsv.
     Under a torch.distributed launch rank 0 projects alone."""
-    import os
-    from . import _policy
-    from ._toml import load_toml
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and int(os.environ.get("RANK", "0")) != 0:
+    if not rank0_only():
         return None
-    res = Path(res_dir)
-    cfg_path = res / FileNameDict["config_file"]
-    if not cfg_path.exists():
-        raise ValueError(f"{cfg_path} is missing: not a result directory of preproc / scan_motif")
-    cfg = load_toml(cfg_path)
-    _policy.apply_config(cfg)
+    res, cfg_path = result_paths(res_dir, made_by="preproc / scan_motif")
+    cfg, _ = load_config(cfg_path)
     vz = cfg["visualization"]
     with open(res / FileNameDict["sample_kmer_pkl_file"], "rb") as fh:
         samp_kh, samp_cnts, samp_label, conseq_list = pickle.load(fh)

@@ -6,7 +6,6 @@ threshold of a p-value exactly (integer DP over all 4^w sequences) and scans the
 leave in the occurrence-CSV contract, so extract_motif_locations and the co-occurrence / density functions read them unchanged.
 Definitions: DESIGN.md section 11.  Host code here is small-matrix arithmetic only; the scan has no CPU path."""
 import math
-import os
 import re
 from decimal import Decimal
 from pathlib import Path
@@ -119,42 +118,42 @@ def min_score_threshold(min_score_bits):
     return int((Decimal(repr(s)) * SCORE_UNIT).to_integral_value(rounding="ROUND_CEILING"))
 
 
-def _scan_pwm(res_dir, matrix_files, p_value=1e-4, min_score=None, pseudocount=1.0, revcom_mode=None, output_dir=None):
-    """`kmap scan_pwm`: config.toml + the encoded reads of a preproc result directory + count matrix files -> pwm.motif_occurence.csv,
-    pwm_conseq.txt, pwm_hits.tsv, pwm_info.csv in output_dir (default res_dir/pwm_scan).  Every matrix is read and its threshold
-    found before the device is touched or a file is written.  Under a torch.distributed launch rank 0 scans alone.
-    Returns [(hits_per_read, positions, scores, strand)] per matrix."""
-    from . import _policy
-    from ._toml import load_toml
-    from .kmer_count import FileNameDict, load_array_pickle
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and int(os.environ.get("RANK", "0")) != 0:
-        return None
-    res = Path(res_dir)
-    cfg_path = res / FileNameDict["config_file"]
-    if not cfg_path.exists():
-        raise ValueError(f"{cfg_path} is missing: not a result directory of preproc")
-    matrix_files = [str(f) for f in matrix_files]
-    if not matrix_files:
-        raise ValueError("scan_pwm: no matrix file given")
-    cfg = load_toml(cfg_path)
-    _policy.apply_config(cfg)
-    revcom = bool(cfg["kmer_count"]["revcom_mode"]) if revcom_mode is None else bool(revcom_mode)
+def load_matrices(matrix_files, pseudocount, p_value, min_score=None, check=None):
+    """[(file, C, W, consensus, t, min_score, max_score)] of count matrix files: weights, the p-value's threshold (min_score given:
+    that one instead) and the score range; check(lo, hi) may refuse a matrix.  A ValueError names the file."""
     motifs = []
     for f in matrix_files:
         C = read_count_matrix(f)
         try:
             W = pwm_weights(C, pseudocount)
             t, lo, hi = pwm_threshold(W, p_value)
+            if check is not None:
+                check(lo, hi)
         except ValueError as exc:
             raise ValueError(f"{f}: {exc}") from None
         if min_score is not None:
             t = min_score_threshold(min_score)
         motifs.append((f, C, W, pwm_consensus(C), t, lo, hi))
+    return motifs
+
+
+def _scan_pwm(res_dir, matrix_files, p_value=1e-4, min_score=None, pseudocount=1.0, revcom_mode=None, output_dir=None):
+    """`kmap scan_pwm`: config.toml + the encoded reads of a preproc result directory + count matrix files -> pwm.motif_occurence.csv,
+    pwm_conseq.txt, pwm_hits.tsv, pwm_info.csv in output_dir (default res_dir/pwm_scan).  Every matrix is read and its threshold
+    found before the device is touched or a file is written.  Under a torch.distributed launch rank 0 scans alone.
+    Returns [(hits_per_read, positions, scores, strand)] per matrix."""
+    from .kmer_count import load_array_pickle, load_config, rank0_only, result_paths
+    if not rank0_only():
+        return None
+    res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
+    matrix_files = [str(f) for f in matrix_files]
+    if not matrix_files:
+        raise ValueError("scan_pwm: no matrix file given")
+    _, revcom = load_config(cfg_path, revcom_mode)
+    motifs = load_matrices(matrix_files, pseudocount, p_value, min_score)
 
     from .motif_discovery import DeviceSeq, write_occurence_file
-    seq = load_array_pickle(res / FileNameDict["processed_fasta_file"])
-    borders = load_array_pickle(res / FileNameDict["processed_fasta_seqboarder_file"])
-    dev_seq = DeviceSeq(seq, borders)
+    dev_seq = DeviceSeq(load_array_pickle(seq_path), load_array_pickle(border_path))
     try:
         per = [dev_seq.scan_pwm(W, t, revcom) for _, _, W, _, t, _, _ in motifs]
         out = res / "pwm_scan" if output_dir is None else Path(output_dir)

@@ -6,7 +6,6 @@ and the count matrix of the selected windows' oriented bases (csrc/pwm_refine.hi
 adds f empty columns on each side first, so a matrix can grow beyond the width of the Hamming ball it came from.  Everything is
 integer equality: no tolerance, no random numbers, two runs write the same bytes.  Host code here is the loop and small-matrix
 arithmetic; the counting has no CPU path."""
-import os
 from pathlib import Path
 
 import numpy as np
@@ -88,15 +87,10 @@ def _refine_pwm(res_dir, matrix_files, flank=0, select="best", p_value=1e-4, pse
     refine_info.csv in output_dir (default res_dir/pwm_refine).  Every matrix is read, padded and its first weights and threshold found
     before the device is touched or a file is written.  Under a torch.distributed launch rank 0 works alone.
     Returns [(result, status, trace)] per matrix."""
-    from . import _policy
-    from ._toml import load_toml
-    from .kmer_count import FileNameDict, load_array_pickle
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and int(os.environ.get("RANK", "0")) != 0:
+    from .kmer_count import load_array_pickle, load_config, rank0_only, result_paths
+    if not rank0_only():
         return None
-    res = Path(res_dir)
-    cfg_path = res / FileNameDict["config_file"]
-    if not cfg_path.exists():
-        raise ValueError(f"{cfg_path} is missing: not a result directory of preproc")
+    res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
     matrix_files = [str(f) for f in matrix_files]
     if not matrix_files:
         raise ValueError("refine_pwm: no matrix file given")
@@ -104,9 +98,7 @@ def _refine_pwm(res_dir, matrix_files, flank=0, select="best", p_value=1e-4, pse
         raise ValueError(f"refine_pwm: select {select!r} is neither 'best' nor 'all'")
     if int(max_iter) != max_iter or max_iter < 1:
         raise ValueError(f"max_iter {max_iter} is not an integer >= 1")
-    cfg = load_toml(cfg_path)
-    _policy.apply_config(cfg)
-    revcom = bool(cfg["kmer_count"]["revcom_mode"]) if revcom_mode is None else bool(revcom_mode)
+    _, revcom = load_config(cfg_path, revcom_mode)
     inputs = []
     for f in matrix_files:
         C0 = read_count_matrix(f)
@@ -117,9 +109,7 @@ def _refine_pwm(res_dir, matrix_files, flank=0, select="best", p_value=1e-4, pse
         inputs.append((f, C0))
 
     from .motif_discovery import DeviceSeq
-    seq = load_array_pickle(res / FileNameDict["processed_fasta_file"])
-    borders = load_array_pickle(res / FileNameDict["processed_fasta_seqboarder_file"])
-    dev_seq = DeviceSeq(seq, borders)
+    dev_seq = DeviceSeq(load_array_pickle(seq_path), load_array_pickle(border_path))
     try:
         runs = [refine_matrix(C0, lambda W, t: dev_seq.pwm_counts(W, t, revcom, select == "best"), flank, p_value, pseudocount, max_iter)
                 for _, C0 in inputs]

@@ -6,7 +6,6 @@ the segment's base counts, klet 2 its first base and its 16 dinucleotide counts 
 does.  Motifs are destroyed; length, GC content, CpG depletion and low-complexity runs stay.  The random draws are counter-based, so a
 (res_dir, klet, seed) names one file.  Host code here is argument checking, the seeds of the copies and the FASTA writer; the shuffle
 has no CPU path."""
-import os
 from pathlib import Path
 
 import numpy as np
@@ -57,14 +56,10 @@ def _shuffle_reads(res_dir, klet=2, seed=0, n_copies=1, output_file=None):
     file (default res_dir/shuffled_control.fa), copy-major, copy c shuffled with copy_seed(seed, c).  Every ValueError is raised
     before the library is loaded or a file is written.  Under a torch.distributed launch rank 0 works alone.  Returns (reads,
     segments, bases, segments unchanged by definition) of one copy."""
-    from .kmer_count import FileNameDict, load_array_pickle
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and int(os.environ.get("RANK", "0")) != 0:
+    from .kmer_count import load_array_pickle, rank0_only, result_paths
+    if not rank0_only():
         return None
-    res = Path(res_dir)
-    seq_path, border_path = res / FileNameDict["processed_fasta_file"], res / FileNameDict["processed_fasta_seqboarder_file"]
-    for p in (seq_path, border_path):
-        if not p.exists():
-            raise ValueError(f"{p} is missing: not a result directory of preproc")
+    res, seq_path, border_path = result_paths(res_dir, config=False, reads=True)
     if isinstance(klet, bool) or int(klet) != klet or int(klet) not in KLETS:
         raise ValueError(f"klet {klet}: 1 (base counts) or 2 (dinucleotide counts) expected")
     if isinstance(n_copies, bool) or int(n_copies) != n_copies or n_copies < 1:

@@ -184,7 +184,7 @@ def res_dir(tmp_path):
 
 
 def test_value_errors_come_before_the_library(res_dir, tmp_path, monkeypatch):
-    from kmap_amd import _ffi, evaluate
+    from kmap_amd import _ffi, pwm
     from kmap_amd.evaluate import _evaluate_pwm
     from kmap_amd.kmer_count import FileNameDict
 
@@ -222,7 +222,7 @@ def test_value_errors_come_before_the_library(res_dir, tmp_path, monkeypatch):
     wide = np.zeros((4, 9), np.int32)
     wide[0], wide[1] = 240_000, -240_000
     with monkeypatch.context() as m:
-        m.setattr(evaluate, "pwm_weights", lambda C, a: wide)
+        m.setattr(pwm, "pwm_weights", lambda C, a: wide)       # load_matrices, the matrix loop the verb shares with scan_pwm
         with pytest.raises(ValueError, match="2\\^22"):
             _evaluate_pwm(res, ctl, **ok)
         wide[1] = -226_000                                   # 9 x 466 000 + 1 = 4 194 001 <= 2^22: the library is what comes next

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import _readscore_model as M
-from tests._refine_model import np_hits, window_scores
+from tests._refine_model import asym_matrix, make_reads, np_hits, window_scores
 
 pytestmark = pytest.mark.gpu
 
@@ -16,31 +16,6 @@ ROOT = Path(__file__).resolve().parent.parent
 GOLD = ROOT / "tests" / "golden"
 MOTIF0, MOTIF1 = GOLD / "report_testfa" / "cntmat_motif0_CAATCGATAGC.csv", GOLD / "report_testfa" / "cntmat_motif1_ACCTACGTA.csv"
 INT32_MIN = -2 ** 31
-
-
-def make_reads(lengths, rng, frac_invalid=0.02, last_separator=True):
-    """reads of the given lengths, a 255 behind each (behind the last one only with last_separator); frac_invalid of the bases are
-    255, among them first and last bases of reads"""
-    lengths = np.asarray(lengths, np.int64)
-    starts = np.concatenate([[0], np.cumsum(lengths + 1)[:-1]])
-    borders = np.stack([starts, starts + lengths], axis=1)
-    n = int((lengths + 1).sum())
-    seq = rng.integers(0, 4, n).astype(np.uint8)
-    seq[rng.random(n) < frac_invalid] = 255
-    nonempty = np.nonzero(lengths > 0)[0]
-    seq[borders[nonempty[::7], 0]] = 255                     # a read's first base
-    seq[borders[nonempty[3::11], 1] - 1] = 255               # a read's last base
-    seq[borders[:, 1]] = 255
-    return (seq, borders) if last_separator else (seq[:-1].copy(), borders)
-
-
-def asym_matrix(w, rng):
-    """random weights whose first column strongly wants A and whose last strongly wants C: a wrong column reversal or a wrong
-    complement changes nearly every score"""
-    W = rng.integers(-300, 201, size=(4, w)).astype(np.int32)
-    W[:, 0] = [200, -400, -410, -420]
-    W[:, -1] = [-430, 200, -440, -450]
-    return W
 
 
 def plant(seq, borders, W, rng, every=5):

@@ -6,70 +6,15 @@ from pathlib import Path
 
 import numpy as np
 import pytest
-from numpy.lib.stride_tricks import sliding_window_view
+
+from tests import _refine_model as M
+from tests._refine_model import asym_matrix, make_reads, np_scan, window_scores
 
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
 GOLD = ROOT / "tests" / "golden"
 MOTIF0, MOTIF1 = GOLD / "report_testfa" / "cntmat_motif0_CAATCGATAGC.csv", GOLD / "report_testfa" / "cntmat_motif1_ACCTACGTA.csv"
-
-
-# ---- the restatement -------------------------------------------------------------------------------------------------------
-def window_scores(seq, W):
-    """(valid, fwd, rc) of every window start 0 .. n - w of the uint8 array"""
-    W = np.asarray(W, np.int64)
-    w = W.shape[1]
-    if len(seq) < w:
-        z = np.zeros(0, np.int64)
-        return np.zeros(0, bool), z, z
-    win = sliding_window_view(np.asarray(seq, np.uint8), w)
-    valid = (win != 255).all(axis=1)
-    x = np.where(win == 255, 0, win).astype(np.int64)
-    cols = np.arange(w)
-    fwd = W[x, cols].sum(axis=1)
-    Wrc = W[::-1, ::-1]                                      # Wrc[b][j] = W[3 - b][w - 1 - j]
-    rc = Wrc[x, cols].sum(axis=1)
-    return valid, fwd, rc
-
-
-def np_scan(seq, borders, W, t, revcom, scored=None):
-    """(hits_per_read, loc, score, strand) as section 11 defines them"""
-    valid, fwd, rc = window_scores(seq, W) if scored is None else scored
-    if revcom:
-        score, minus = np.maximum(fwd, rc), rc > fwd        # a tie is '+'
-    else:
-        score, minus = fwd, np.zeros(len(fwd), bool)
-    p = np.nonzero(valid & (score >= t))[0]
-    borders = np.asarray(borders, np.int64).reshape(-1, 2)
-    r = np.searchsorted(borders[:, 0], p, side="right") - 1  # the last read that starts at or before the window
-    assert (p + np.asarray(W).shape[1] <= borders[r, 1]).all()  # a valid window lies inside its read: the 255 behind every read
-    hits = np.bincount(r, minlength=len(borders)).astype(np.int32)
-    return hits, (p - borders[r, 0]).astype(np.int32), score[p].astype(np.int32), minus[p].astype(np.uint8)
-
-
-def make_reads(lengths, rng, frac_invalid=0.02):
-    """reads of the given lengths, a 255 behind each; frac_invalid of the bases are 255, among them first and last bases of reads"""
-    lengths = np.asarray(lengths, np.int64)
-    starts = np.concatenate([[0], np.cumsum(lengths + 1)[:-1]])
-    borders = np.stack([starts, starts + lengths], axis=1)
-    n = int((lengths + 1).sum())
-    seq = rng.integers(0, 4, n).astype(np.uint8)
-    seq[rng.random(n) < frac_invalid] = 255
-    nonempty = np.nonzero(lengths > 0)[0]
-    seq[borders[nonempty[::7], 0]] = 255                     # a read's first base
-    seq[borders[nonempty[3::11], 1] - 1] = 255               # a read's last base
-    seq[borders[:, 1]] = 255
-    return seq, borders
-
-
-def asym_matrix(w, rng):
-    """random weights whose first column strongly wants A and whose last strongly wants C: a wrong column reversal or a wrong
-    complement changes nearly every score"""
-    W = rng.integers(-300, 201, size=(4, w)).astype(np.int32)
-    W[:, 0] = [200, -400, -410, -420]
-    W[:, -1] = [-430, 200, -440, -450]
-    return W
 
 
 def check(got, want):
@@ -120,6 +65,28 @@ def test_kernel_against_numpy(w, revcom):
             assert 0 < n < 0.1 * valid.sum()
     if not revcom:
         assert not ds.scan_pwm(W, lo, False)[3].any()
+
+
+# ---- 1b. the sparse traversal at the group, wave-tile and block edges ------------------------------------------------------------
+@pytest.mark.parametrize("w", [9, 31])
+@pytest.mark.parametrize("shift", [-1, 0, 1])
+def test_read_starts_at_tile_edges(shift, w):
+    """reads that start exactly at 16, 1024, 2048, 4096 and 5136 (+ shift), tests/_refine_model.py edge_reads: every window a hit (a
+    lane walks all 16 bits and every border) and one in ten (the search for a lane's first hit places the read)"""
+    from kmap_amd.motif_discovery import DeviceSeq
+    seq, borders, W, scored, _ = M.edge_reads(shift, w)
+    valid, fwd, rc = scored
+    lo = int(W.min(axis=0).sum())
+    ds = DeviceSeq(seq, borders)
+    try:
+        for revcom in (True, False):
+            M.check_edge_hits(shift, w, M.np_hits(seq, borders, W, lo, revcom, scored), revcom)
+            for t in (lo, int(np.quantile((np.maximum(fwd, rc) if revcom else fwd)[valid], 0.9))):
+                want = np_scan(seq, borders, W, t, revcom, scored)
+                assert (len(want[1]) == valid.sum()) if t == lo else (0 < len(want[1]) < 0.2 * valid.sum())
+                check(ds.scan_pwm(W, t, revcom), want)
+    finally:
+        ds.close()
 
 
 # ---- 2. more than 65 535 reads -----------------------------------------------------------------------------------------------

@@ -8,37 +8,13 @@ import numpy as np
 import pytest
 
 from tests import _refine_model as M
+from tests._refine_model import asym_matrix, make_reads
 
 pytestmark = pytest.mark.gpu
 
 ROOT = Path(__file__).resolve().parent.parent
 GOLD = ROOT / "tests" / "golden"
 MOTIF0, MOTIF1 = GOLD / "report_testfa" / "cntmat_motif0_CAATCGATAGC.csv", GOLD / "report_testfa" / "cntmat_motif1_ACCTACGTA.csv"
-
-
-def make_reads(lengths, rng, frac_invalid=0.02):
-    """reads of the given lengths, a 255 behind each; frac_invalid of the bases are 255, among them first and last bases of reads
-    (the recipe of tests/test_gpu_pwm.py)"""
-    lengths = np.asarray(lengths, np.int64)
-    starts = np.concatenate([[0], np.cumsum(lengths + 1)[:-1]])
-    borders = np.stack([starts, starts + lengths], axis=1)
-    n = int((lengths + 1).sum())
-    seq = rng.integers(0, 4, n).astype(np.uint8)
-    seq[rng.random(n) < frac_invalid] = 255
-    nonempty = np.nonzero(lengths > 0)[0]
-    seq[borders[nonempty[::7], 0]] = 255                     # a read's first base
-    seq[borders[nonempty[3::11], 1] - 1] = 255               # a read's last base
-    seq[borders[:, 1]] = 255
-    return seq, borders
-
-
-def asym_matrix(w, rng):
-    """random weights whose first column strongly wants A and whose last strongly wants C: a wrong column reversal or a wrong
-    complement changes nearly every score"""
-    W = rng.integers(-300, 201, size=(4, w)).astype(np.int32)
-    W[:, 0] = [200, -400, -410, -420]
-    W[:, -1] = [-430, 200, -440, -450]
-    return W
 
 
 def check(got, want):
@@ -100,6 +76,29 @@ def test_kernel_against_model(w, revcom):
                 assert 0 < n_minus < n_sel
             else:
                 assert n_minus == 0
+
+
+# ---- 1b. the sparse traversal at the group, wave-tile and block edges ------------------------------------------------------------
+@pytest.mark.parametrize("w", [9, 31])
+@pytest.mark.parametrize("shift", [-1, 0, 1])
+def test_read_starts_at_tile_edges(shift, w):
+    """reads that start exactly at 16, 1024, 2048, 4096 and 5136 (+ shift), tests/_refine_model.py edge_reads: every window a hit (a
+    lane walks all 16 bits and every border) and one in ten (the search for a lane's first hit places the read)"""
+    from kmap_amd.motif_discovery import DeviceSeq
+    seq, borders, W, scored, _ = M.edge_reads(shift, w)
+    valid, fwd, rc = scored
+    lo = int(W.min(axis=0).sum())
+    ds = DeviceSeq(seq, borders)
+    try:
+        for revcom in (True, False):
+            M.check_edge_hits(shift, w, M.np_hits(seq, borders, W, lo, revcom, scored), revcom)
+            for t in (lo, int(np.quantile((np.maximum(fwd, rc) if revcom else fwd)[valid], 0.9))):
+                for best in (True, False):
+                    want = M.np_counts(seq, borders, W, t, revcom, best, scored)
+                    assert (want[1] == valid.sum()) if t == lo else (0 < want[1] < 0.2 * valid.sum())
+                    check(ds.pwm_counts(W, t, revcom, best), want)
+    finally:
+        ds.close()
 
 
 # ---- 2. ties --------------------------------------------------------------------------------------------------------------------

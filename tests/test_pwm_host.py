@@ -164,7 +164,7 @@ def test_min_score_threshold_is_the_decimal_ceiling():
 def test_only_rank_zero_scans_and_bad_input_writes_nothing(tmp_path, monkeypatch):
     """the other ranks of a torch.distributed launch return at once; a bad matrix is reported before any output exists"""
     from kmap_amd._toml import dump_toml
-    from kmap_amd.kmer_count import read_default_config_file
+    from kmap_amd.kmer_count import FileNameDict, read_default_config_file
     from kmap_amd.pwm import _scan_pwm
     monkeypatch.setenv("WORLD_SIZE", "2")
     monkeypatch.setenv("RANK", "1")
@@ -177,6 +177,11 @@ def test_only_rank_zero_scans_and_bad_input_writes_nothing(tmp_path, monkeypatch
     res = tmp_path / "res"
     res.mkdir()
     dump_toml(read_default_config_file(), res / "config.toml")
+    reads = [FileNameDict["processed_fasta_file"], FileNameDict["processed_fasta_seqboarder_file"]]
+    for name in reads:                       # the two read files are looked for before a matrix is read or the device touched
+        with pytest.raises(ValueError, match=re.escape(name) + " is missing: not a result directory of preproc"):
+            _scan_pwm(str(res), [str(MOTIF0)], output_dir=str(tmp_path / "out"))
+        (res / name).write_bytes(b"")
     bad = tmp_path / "bad_matrix.csv"
     bad.write_text("1,2,3,4\n1,2,3,4\n1,2,3,4\n")
     with pytest.raises(ValueError, match=r"bad_matrix\.csv"):
@@ -185,7 +190,7 @@ def test_only_rank_zero_scans_and_bad_input_writes_nothing(tmp_path, monkeypatch
     zero.write_text("5,0,1,2\n1,9,1,2\n1,1,7,2\n1,1,1,2\n")
     with pytest.raises(ValueError, match=r"zero\.csv.*zero count"):
         _scan_pwm(str(res), [str(zero)], pseudocount=0.0, output_dir=str(tmp_path / "out"))
-    assert not (tmp_path / "out").exists() and sorted(p.name for p in res.iterdir()) == ["config.toml"]
+    assert not (tmp_path / "out").exists() and sorted(p.name for p in res.iterdir()) == sorted(["config.toml"] + reads)
 
 
 def test_cli_lists_scan_pwm():

@@ -159,7 +159,7 @@ def test_written_matrix_round_trips(tmp_path, testfa):
 
 def test_verb_checks_its_input_before_the_device(tmp_path, monkeypatch):
     from kmap_amd._toml import dump_toml
-    from kmap_amd.kmer_count import read_default_config_file
+    from kmap_amd.kmer_count import FileNameDict, read_default_config_file
     from kmap_amd.refine import _refine_pwm
     monkeypatch.setenv("WORLD_SIZE", "2")
     monkeypatch.setenv("RANK", "1")
@@ -173,6 +173,11 @@ def test_verb_checks_its_input_before_the_device(tmp_path, monkeypatch):
     res.mkdir()
     dump_toml(read_default_config_file(), res / "config.toml")
     out = tmp_path / "out"
+    reads = [FileNameDict["processed_fasta_file"], FileNameDict["processed_fasta_seqboarder_file"]]
+    for name in reads:                       # the two read files are looked for before a matrix is read or the device touched
+        with pytest.raises(ValueError, match=re.escape(name) + " is missing: not a result directory of preproc"):
+            _refine_pwm(str(res), [str(MOTIF0)], output_dir=str(out))
+        (res / name).write_bytes(b"")
     with pytest.raises(ValueError, match="no matrix file"):
         _refine_pwm(str(res), [], output_dir=str(out))
     with pytest.raises(ValueError, match="select"):
@@ -183,7 +188,7 @@ def test_verb_checks_its_input_before_the_device(tmp_path, monkeypatch):
         _refine_pwm(str(res), [str(MOTIF1), str(MOTIF0)], flank=11, output_dir=str(out))     # 9 + 22 = 31 passes, 11 + 22 does not
     with pytest.raises(ValueError, match=r"cntmat_motif1.*zero count"):
         _refine_pwm(str(res), [str(MOTIF1)], flank=1, pseudocount=0.0, output_dir=str(out))
-    assert not out.exists() and sorted(p.name for p in res.iterdir()) == ["config.toml"]
+    assert not out.exists() and sorted(p.name for p in res.iterdir()) == sorted(["config.toml"] + reads)
 
 
 def test_cli_lists_refine_pwm():
