@@ -63,11 +63,21 @@ struct DevBuf {
         }
         return KMAP_OK;
     }
-    ~DevBuf() {
+    void release() {                       // frees now what the destructor would free later; alloc() may follow
         if (p) (void)hipFree(p);
+        p = nullptr;
     }
+    ~DevBuf() { release(); }
     template <typename T>
     T *as() { return (T *)p; }
+};
+// RAII event, for the same entry points
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    hipError_t create() { return hipEventCreate(&e); }
+    ~DevEvent() {
+        if (e) (void)hipEventDestroy(e);
+    }
 };
 
 // ---- device helpers ---------------------------------------------------------------------------

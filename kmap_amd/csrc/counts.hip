@@ -519,10 +519,8 @@ static int compact_range(kmap_counts *c, int k, int merge, uint64_t first, uint6
     } else {
         compact_count_kernel<<<nblk, BLK, 0, st>>>(bins, n_bins, k, merge, bc, nb, first, kr);
     }
-    KMAP_TRY(exclusive_scan_u32(bc, nb, boff, st));
     uint64_t total = 0;
-    KMAP_CHECK_HIP(hipMemcpyAsync(&total, boff + nb, 8, hipMemcpyDeviceToHost, st));
-    KMAP_CHECK_HIP(hipStreamSynchronize(st));
+    KMAP_TRY(exclusive_scan_total(bc, nb, boff, &total, st));
     KMAP_TRY(kmap_counts_reserve_table(c, (size_t)total));
     if (total) {
         if (k < 16) compact_write_kernel<uint32_t><<<nblk, BLK, 0, st>>>(bins, n_bins, k, merge, boff, (uint32_t *)c->uniq, c->cnt, first, kr);

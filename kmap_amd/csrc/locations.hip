@@ -8,15 +8,15 @@
 //   3. key kernel: (consensus, chrom rank, start, end - start, name key) packed LSB-first into 128 bits with widths the host chose;
 //      the name key holds the decimal digits of seq_ind as (digit + 1) nibbles, most significant first, zero-padded, so that the
 //      integer order of the keys is the string order of "motif_{i}_{seq_ind}".  The same pass ORs / ANDs all keys.
-//   4. stable LSD radix sort of (key, interval index), 8-bit digits, in the style of counts_sort.hip; a digit that is the same in
-//      every key (its bits of OR ^ AND are zero) is skipped
+//   4. stable LSD radix sort of (key, interval index), 8-bit digits (radix_sort.h, two key words + payload); a digit that is the same
+//      in every key (its bits of OR ^ AND are zero) is skipped
 //   5. gather of the sorted (seq_ind, start, end) triples
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "scan_util.h"
+#include "radix_sort.h"
 
 namespace {
 constexpr int BLK = 256;
@@ -145,72 +145,6 @@ __global__ __launch_bounds__(BLK) void loc_key_kernel(const uint32_t *__restrict
     }
 }
 
-// ---- stable LSD radix sort of (128-bit key, uint32 value), 8-bit digits (counts_sort.hip's scheme, two key words) -------------
-constexpr int RS_ITEMS = 16, RS_TILE = KMAP_WAVE * RS_ITEMS, RS_WAVES = 4;
-__device__ __forceinline__ uint32_t digit_of(uint64_t lo, uint64_t hi, int shift) {
-    return (uint32_t)((shift < 64 ? lo >> shift : hi >> (shift - 64)) & 255u);
-}
-__global__ __launch_bounds__(KMAP_WAVE *RS_WAVES) void lrs_hist_kernel(const uint64_t *__restrict__ klo, const uint64_t *__restrict__ khi,
-                                                                       int64_t n, int shift, int64_t n_tiles, uint32_t *__restrict__ counts) {
-    __shared__ uint32_t cnt[RS_WAVES][256];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t tile = (int64_t)blockIdx.x * RS_WAVES + wave;
-    const uint64_t *__restrict__ kw = shift < 64 ? klo : khi;
-    const int sh = shift & 63;
-    for (int d = lane; d < 256; d += 64) cnt[wave][d] = 0;
-    __builtin_amdgcn_wave_barrier();
-    if (tile < n_tiles) {
-#pragma unroll
-        for (int i = 0; i < RS_ITEMS; ++i) {
-            const int64_t at = tile * RS_TILE + (int64_t)i * KMAP_WAVE + lane;
-            if (at < n) atomicAdd(&cnt[wave][(kw[at] >> sh) & 255u], 1u);
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    if (tile < n_tiles)
-        for (int d = lane; d < 256; d += 64) counts[(int64_t)d * n_tiles + tile] = cnt[wave][d];
-}
-__global__ __launch_bounds__(KMAP_WAVE *RS_WAVES) void lrs_scatter_kernel(const uint64_t *__restrict__ klo, const uint64_t *__restrict__ khi,
-                                                                          const uint32_t *__restrict__ val, int64_t n, int shift, int64_t n_tiles,
-                                                                          const uint64_t *__restrict__ offs, uint64_t *__restrict__ olo,
-                                                                          uint64_t *__restrict__ ohi, uint32_t *__restrict__ oval) {
-    __shared__ uint32_t cnt[RS_WAVES][256];
-    __shared__ uint64_t base[RS_WAVES][256];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t tile = (int64_t)blockIdx.x * RS_WAVES + wave;
-    if (tile >= n_tiles) return;                                          // wave-uniform; no block-wide barrier below
-    for (int d = lane; d < 256; d += 64) {
-        cnt[wave][d] = 0;
-        base[wave][d] = offs[(int64_t)d * n_tiles + tile];
-    }
-    __builtin_amdgcn_wave_barrier();
-    const unsigned long long lt = (1ull << lane) - 1ull;
-#pragma unroll 4
-    for (int i = 0; i < RS_ITEMS; ++i) {
-        const int64_t at = tile * RS_TILE + (int64_t)i * KMAP_WAVE + lane;
-        const bool live = at < n;
-        const uint64_t lo = live ? klo[at] : 0ull, hi = live ? khi[at] : 0ull;
-        const uint32_t dg = digit_of(lo, hi, shift);
-        unsigned long long same = __ballot(live);                         // lanes with this lane's digit (and a key)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long bal = __ballot((dg >> b) & 1u);
-            same &= ((dg >> b) & 1u) ? bal : ~bal;
-        }
-        if (live) {
-            const uint32_t old = cnt[wave][dg];                           // the group's lanes all read the count before its leader bumps it
-            const uint32_t rank = old + (uint32_t)__popcll(same & lt);
-            if ((same & lt) == 0ull) cnt[wave][dg] = old + (uint32_t)__popcll(same);
-            const uint64_t to = base[wave][dg] + rank;
-            olo[to] = lo;
-            ohi[to] = hi;
-            oval[to] = val[at];
-        }
-        __builtin_amdgcn_wave_barrier();                                  // LDS operations of a wave execute in order: item i + 1 sees the bump
-    }
-}
-
 __global__ __launch_bounds__(BLK) void loc_gather_kernel(const uint32_t *__restrict__ idx, int64_t m_total, const int64_t *__restrict__ v_row,
                                                          const int64_t *__restrict__ v_start, const int64_t *__restrict__ v_end,
                                                          int64_t *__restrict__ o_row, int64_t *__restrict__ o_start, int64_t *__restrict__ o_end) {
@@ -290,125 +224,96 @@ static int locations_impl(int64_t n_rows, int n_cons, const int32_t *const *hits
     KMAP_REQUIRE(n_cells < ((int64_t)1 << 40), "locations: too many cells");
 
     // ---- device buffers
-    std::vector<void *> allocs;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto cleanup = [&]() {
-        for (void *p : allocs) (void)hipFree(p);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    };
-    auto fail = [&](hipError_t e, const char *what) {
-        kmap_set_error("locations: %s: %s", what, hipGetErrorString(e));
-        cleanup();
-        return e == hipErrorOutOfMemory ? KMAP_E_NOMEM : KMAP_E_HIP;
-    };
-#define TRYH(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(_e, #expr); } while (0)
-#define TRYK(expr) do { int _r = (expr); if (_r != KMAP_OK) { cleanup(); return _r; } } while (0)
-    auto dalloc = [&](void **p, size_t bytes) {
-        hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-        if (e == hipSuccess) allocs.push_back(*p);
-        return e;
-    };
     hipStream_t st = nullptr;
-    TRYH(hipEventCreate(&ev0));
-    TRYH(hipEventCreate(&ev1));
-    TRYH(hipEventRecord(ev0, st));
-    uint32_t *hits_d, *flag, *first;
-    int32_t *pos_d, *clen_d, *crank_d;
-    int64_t *cb_d, *seq_d, *bstart_d;
-    uint64_t *offs, *ioff, *bounds_d;
-    TRYH(dalloc((void **)&hits_d, (size_t)n_cells * 4));
-    TRYH(dalloc((void **)&offs, ((size_t)n_cells + 1) * 8));
-    TRYH(dalloc((void **)&pos_d, (size_t)P * 4));
-    TRYH(dalloc((void **)&flag, (size_t)P * 4));
-    TRYH(dalloc((void **)&ioff, ((size_t)P + 1) * 8));
-    TRYH(dalloc((void **)&cb_d, ((size_t)n_cons + 1) * 8));
-    TRYH(dalloc((void **)&bounds_d, ((size_t)n_cons + 1) * 8));
-    TRYH(dalloc((void **)&clen_d, (size_t)n_cons * 4));
-    TRYH(dalloc((void **)&seq_d, (size_t)n_rows * 8));
-    TRYH(dalloc((void **)&bstart_d, (size_t)n_bed * 8));
-    TRYH(dalloc((void **)&crank_d, (size_t)n_bed * 4));
+    DevEvent ev0, ev1;
+    KMAP_CHECK_HIP(ev0.create());
+    KMAP_CHECK_HIP(ev1.create());
+    KMAP_CHECK_HIP(hipEventRecord(ev0.e, st));
+    DevBuf hits_d, offs, pos_d, flag, ioff, cb_d, bounds_d, clen_d, seq_d, bstart_d, crank_d;
+    KMAP_TRY(hits_d.alloc((size_t)n_cells * 4));
+    KMAP_TRY(offs.alloc(((size_t)n_cells + 1) * 8));
+    KMAP_TRY(pos_d.alloc((size_t)P * 4));
+    KMAP_TRY(flag.alloc((size_t)P * 4));
+    KMAP_TRY(ioff.alloc(((size_t)P + 1) * 8));
+    KMAP_TRY(cb_d.alloc(((size_t)n_cons + 1) * 8));
+    KMAP_TRY(bounds_d.alloc(((size_t)n_cons + 1) * 8));
+    KMAP_TRY(clen_d.alloc((size_t)n_cons * 4));
+    KMAP_TRY(seq_d.alloc((size_t)n_rows * 8));
+    KMAP_TRY(bstart_d.alloc((size_t)n_bed * 8));
+    KMAP_TRY(crank_d.alloc((size_t)n_bed * 4));
     for (int c = 0; c < n_cons; ++c) {
-        TRYH(hipMemcpyAsync(hits_d + (size_t)c * n_rows, hits[c], (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
-        if (n_pos[c]) TRYH(hipMemcpyAsync(pos_d + cb[(size_t)c], pos[c], (size_t)n_pos[c] * 4, hipMemcpyHostToDevice, st));
+        KMAP_CHECK_HIP(hipMemcpyAsync(hits_d.as<uint32_t>() + (size_t)c * n_rows, hits[c], (size_t)n_rows * 4, hipMemcpyHostToDevice, st));
+        if (n_pos[c])
+            KMAP_CHECK_HIP(hipMemcpyAsync(pos_d.as<int32_t>() + cb[(size_t)c], pos[c], (size_t)n_pos[c] * 4, hipMemcpyHostToDevice, st));
     }
-    TRYH(hipMemcpyAsync(cb_d, cb.data(), ((size_t)n_cons + 1) * 8, hipMemcpyHostToDevice, st));
-    TRYH(hipMemcpyAsync(clen_d, cons_len, (size_t)n_cons * 4, hipMemcpyHostToDevice, st));
-    TRYH(hipMemcpyAsync(seq_d, seq_ind, (size_t)n_rows * 8, hipMemcpyHostToDevice, st));
+    KMAP_CHECK_HIP(hipMemcpyAsync(cb_d.p, cb.data(), ((size_t)n_cons + 1) * 8, hipMemcpyHostToDevice, st));
+    KMAP_CHECK_HIP(hipMemcpyAsync(clen_d.p, cons_len, (size_t)n_cons * 4, hipMemcpyHostToDevice, st));
+    KMAP_CHECK_HIP(hipMemcpyAsync(seq_d.p, seq_ind, (size_t)n_rows * 8, hipMemcpyHostToDevice, st));
     if (n_bed) {
-        TRYH(hipMemcpyAsync(bstart_d, bed_start, (size_t)n_bed * 8, hipMemcpyHostToDevice, st));
-        TRYH(hipMemcpyAsync(crank_d, chrom_rank, (size_t)n_bed * 4, hipMemcpyHostToDevice, st));
+        KMAP_CHECK_HIP(hipMemcpyAsync(bstart_d.p, bed_start, (size_t)n_bed * 8, hipMemcpyHostToDevice, st));
+        KMAP_CHECK_HIP(hipMemcpyAsync(crank_d.p, chrom_rank, (size_t)n_bed * 4, hipMemcpyHostToDevice, st));
     }
     // ---- 1-2: interval starts
-    TRYK(exclusive_scan_u32(hits_d, n_cells, offs, st));
+    KMAP_TRY(exclusive_scan_u32(hits_d.as<uint32_t>(), n_cells, offs.as<uint64_t>(), st));
     const unsigned gp = (unsigned)((P + BLK - 1) / BLK);
-    loc_flag_kernel<<<gp, BLK, 0, st>>>(pos_d, P, cb_d, n_cons, clen_d, flag);
-    loc_head_kernel<<<(unsigned)((n_cells + BLK - 1) / BLK), BLK, 0, st>>>(hits_d, offs, n_cells, flag);
-    TRYK(exclusive_scan_u32(flag, P, ioff, st));
-    loc_bounds_kernel<<<(unsigned)((n_cons + 1 + 63) / 64), 64, 0, st>>>(ioff, cb_d, n_cons, bounds_d);
+    loc_flag_kernel<<<gp, BLK, 0, st>>>(pos_d.as<int32_t>(), P, cb_d.as<int64_t>(), n_cons, clen_d.as<int32_t>(), flag.as<uint32_t>());
+    loc_head_kernel<<<(unsigned)((n_cells + BLK - 1) / BLK), BLK, 0, st>>>(hits_d.as<uint32_t>(), offs.as<uint64_t>(), n_cells,
+                                                                           flag.as<uint32_t>());
+    KMAP_TRY(exclusive_scan_u32(flag.as<uint32_t>(), P, ioff.as<uint64_t>(), st));
+    loc_bounds_kernel<<<(unsigned)((n_cons + 1 + 63) / 64), 64, 0, st>>>(ioff.as<uint64_t>(), cb_d.as<int64_t>(), n_cons,
+                                                                         bounds_d.as<uint64_t>());
     std::vector<uint64_t> bounds((size_t)n_cons + 1);
-    TRYH(hipMemcpyAsync(bounds.data(), bounds_d, ((size_t)n_cons + 1) * 8, hipMemcpyDeviceToHost, st));
-    TRYH(hipStreamSynchronize(st));
-    TRYH(hipGetLastError());
+    KMAP_CHECK_HIP(hipMemcpyAsync(bounds.data(), bounds_d.p, ((size_t)n_cons + 1) * 8, hipMemcpyDeviceToHost, st));
+    KMAP_CHECK_HIP(hipStreamSynchronize(st));
+    KMAP_CHECK_HIP(hipGetLastError());
     const int64_t M = (int64_t)bounds[(size_t)n_cons];
-    TRYH(dalloc((void **)&first, (size_t)M * 4));
-    loc_first_kernel<<<gp, BLK, 0, st>>>(flag, ioff, P, first);
+    DevBuf first;
+    KMAP_TRY(first.alloc((size_t)M * 4));
+    loc_first_kernel<<<gp, BLK, 0, st>>>(flag.as<uint32_t>(), ioff.as<uint64_t>(), P, first.as<uint32_t>());
     // ---- 3: keys
-    uint64_t *klo, *khi, *klo2, *khi2;
-    uint32_t *idx, *idx2;
-    int64_t *v_row, *v_start, *v_end;
-    unsigned long long *orand;
-    TRYH(dalloc((void **)&klo, (size_t)M * 8));
-    TRYH(dalloc((void **)&khi, (size_t)M * 8));
-    TRYH(dalloc((void **)&klo2, (size_t)M * 8));
-    TRYH(dalloc((void **)&khi2, (size_t)M * 8));
-    TRYH(dalloc((void **)&idx, (size_t)M * 4));
-    TRYH(dalloc((void **)&idx2, (size_t)M * 4));
-    TRYH(dalloc((void **)&v_row, (size_t)M * 8));
-    TRYH(dalloc((void **)&v_start, (size_t)M * 8));
-    TRYH(dalloc((void **)&v_end, (size_t)M * 8));
-    TRYH(dalloc((void **)&orand, 32));
-    TRYH(hipMemsetAsync(orand, 0, 16, st));
-    TRYH(hipMemsetAsync(orand + 2, 0xff, 16, st));
+    DevBuf klo, khi, klo2, khi2, idx, idx2, v_row, v_start, v_end, orand;
+    KMAP_TRY(klo.alloc((size_t)M * 8));
+    KMAP_TRY(khi.alloc((size_t)M * 8));
+    KMAP_TRY(klo2.alloc((size_t)M * 8));
+    KMAP_TRY(khi2.alloc((size_t)M * 8));
+    KMAP_TRY(idx.alloc((size_t)M * 4));
+    KMAP_TRY(idx2.alloc((size_t)M * 4));
+    KMAP_TRY(v_row.alloc((size_t)M * 8));
+    KMAP_TRY(v_start.alloc((size_t)M * 8));
+    KMAP_TRY(v_end.alloc((size_t)M * 8));
+    KMAP_TRY(orand.alloc(32));
+    KMAP_CHECK_HIP(hipMemsetAsync(orand.p, 0, 16, st));
+    KMAP_CHECK_HIP(hipMemsetAsync(orand.as<unsigned long long>() + 2, 0xff, 16, st));
     const unsigned gk = (unsigned)std::min<int64_t>((M + BLK - 1) / BLK, 4096);
-    loc_key_kernel<<<gk, BLK, 0, st>>>(first, M, P, offs, n_cells, n_rows, pos_d, clen_d, seq_d, bstart_d, crank_d, L, klo, khi, idx,
-                                       v_row, v_start, v_end, orand);
+    loc_key_kernel<<<gk, BLK, 0, st>>>(first.as<uint32_t>(), M, P, offs.as<uint64_t>(), n_cells, n_rows, pos_d.as<int32_t>(),
+                                       clen_d.as<int32_t>(), seq_d.as<int64_t>(), bstart_d.as<int64_t>(), crank_d.as<int32_t>(), L,
+                                       klo.as<uint64_t>(), khi.as<uint64_t>(), idx.as<uint32_t>(), v_row.as<int64_t>(),
+                                       v_start.as<int64_t>(), v_end.as<int64_t>(), orand.as<unsigned long long>());
     unsigned long long oa[4];
-    TRYH(hipMemcpyAsync(oa, orand, 32, hipMemcpyDeviceToHost, st));
-    TRYH(hipStreamSynchronize(st));
-    TRYH(hipGetLastError());
+    KMAP_CHECK_HIP(hipMemcpyAsync(oa, orand.p, 32, hipMemcpyDeviceToHost, st));
+    KMAP_CHECK_HIP(hipStreamSynchronize(st));
+    KMAP_CHECK_HIP(hipGetLastError());
     // ---- 4: radix passes over the digits that differ between keys
-    const int64_t n_tiles = (M + RS_TILE - 1) / RS_TILE;
-    const unsigned gridt = (unsigned)((n_tiles + RS_WAVES - 1) / RS_WAVES);
-    uint32_t *counts;
-    uint64_t *roffs;
-    TRYH(dalloc((void **)&counts, (size_t)256 * n_tiles * 4));
-    TRYH(dalloc((void **)&roffs, ((size_t)256 * n_tiles + 1) * 8));
+    RsBufs<2, true> ping{{klo.as<uint64_t>(), khi.as<uint64_t>()}, idx.as<uint32_t>()};
+    RsBufs<2, true> pong{{klo2.as<uint64_t>(), khi2.as<uint64_t>()}, idx2.as<uint32_t>()};
     const uint64_t diff[2] = {(uint64_t)(oa[0] ^ oa[2]), (uint64_t)(oa[1] ^ oa[3])};
-    for (int shift = 0; shift < 128; shift += 8) {
-        if (((diff[shift >> 6] >> (shift & 63)) & 255u) == 0) continue;
-        lrs_hist_kernel<<<gridt, KMAP_WAVE * RS_WAVES, 0, st>>>(klo, khi, M, shift, n_tiles, counts);
-        TRYK(exclusive_scan_u32(counts, 256 * n_tiles, roffs, st));
-        lrs_scatter_kernel<<<gridt, KMAP_WAVE * RS_WAVES, 0, st>>>(klo, khi, idx, M, shift, n_tiles, roffs, klo2, khi2, idx2);
-        std::swap(klo, klo2);
-        std::swap(khi, khi2);
-        std::swap(idx, idx2);
-    }
-    // ---- 5: gather the sorted triples (into the buffers of the second key word, no longer needed)
-    int64_t *o_row = (int64_t *)klo2, *o_start = (int64_t *)khi2, *o_end;
-    TRYH(dalloc((void **)&o_end, (size_t)M * 8));
-    loc_gather_kernel<<<(unsigned)((M + BLK - 1) / BLK), BLK, 0, st>>>(idx, M, v_row, v_start, v_end, o_row, o_start, o_end);
-    TRYH(hipGetLastError());
-    TRYH(hipMemcpyAsync(out_row, o_row, (size_t)M * 8, hipMemcpyDeviceToHost, st));
-    TRYH(hipMemcpyAsync(out_start, o_start, (size_t)M * 8, hipMemcpyDeviceToHost, st));
-    TRYH(hipMemcpyAsync(out_end, o_end, (size_t)M * 8, hipMemcpyDeviceToHost, st));
-    TRYH(hipEventRecord(ev1, st));
-    TRYH(hipStreamSynchronize(st));
+    KMAP_TRY(radix_sort(ping, pong, M, diff, st));
+    // ---- 5: gather the sorted triples.  Only ping's payload is read from here on, so the rows and starts go into pong's two key
+    // words -- the set that does not hold the result, whichever pair of allocations that is after the swaps -- and need no buffers
+    // of their own
+    int64_t *o_row = (int64_t *)pong.w[0], *o_start = (int64_t *)pong.w[1];
+    DevBuf o_end;
+    KMAP_TRY(o_end.alloc((size_t)M * 8));
+    loc_gather_kernel<<<(unsigned)((M + BLK - 1) / BLK), BLK, 0, st>>>(ping.val, M, v_row.as<int64_t>(), v_start.as<int64_t>(),
+                                                                       v_end.as<int64_t>(), o_row, o_start, o_end.as<int64_t>());
+    KMAP_CHECK_HIP(hipGetLastError());
+    KMAP_CHECK_HIP(hipMemcpyAsync(out_row, o_row, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+    KMAP_CHECK_HIP(hipMemcpyAsync(out_start, o_start, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+    KMAP_CHECK_HIP(hipMemcpyAsync(out_end, o_end.p, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+    KMAP_CHECK_HIP(hipEventRecord(ev1.e, st));
+    KMAP_CHECK_HIP(hipStreamSynchronize(st));
     for (int c = 0; c < n_cons; ++c) n_per_cons[c] = (int64_t)(bounds[(size_t)c + 1] - bounds[(size_t)c]);
-    if (device_ms) TRYH(hipEventElapsedTime(device_ms, ev0, ev1));
-#undef TRYH
-#undef TRYK
-    cleanup();
+    if (device_ms) KMAP_CHECK_HIP(hipEventElapsedTime(device_ms, ev0.e, ev1.e));
     return KMAP_OK;
 }
 

@@ -122,10 +122,8 @@ int hamball_core(const H *u_dev, const CT *c_dev, int64_t n, int k, uint64_t con
         for (int p = 0; p < k; ++p) rc = (H)((rc << 2) | ((com >> (2 * p)) & 3));
     }
     hamball_count_kernel<H><<<nb, HB_TPB, 0, st>>>(u_dev, n, ch, rc, k, radius, revcom, bc);
-    KMAP_TRY(exclusive_scan_u32(bc, nb, boff, st));
     uint64_t total = 0;
-    KMAP_CHECK_HIP(hipMemcpyAsync(&total, boff + nb, 8, hipMemcpyDeviceToHost, st));
-    KMAP_CHECK_HIP(hipStreamSynchronize(st));
+    KMAP_TRY(exclusive_scan_total(bc, nb, boff, &total, st));
     KMAP_TRY(ou.alloc((size_t)total * sizeof(H)));
     KMAP_TRY(oc.alloc((size_t)total * sizeof(CT)));
     hamball_write_kernel<H, CT><<<nb, HB_TPB, 0, st>>>(u_dev, c_dev, n, ch, rc, k, radius, revcom, boff, ou.as<H>(), oc.as<CT>(),

@@ -96,4 +96,11 @@ inline int exclusive_scan_u32(const uint32_t *in, int64_t n, uint64_t *out, hipS
     scan_tiles_kernel<<<(unsigned)tiles, SCAN_TPB, 0, st>>>(in, n, toff, out);
     return KMAP_OK;
 }
+// the same, then *total = out[n] on the host: returns after st has been synchronised
+inline int exclusive_scan_total(const uint32_t *in, int64_t n, uint64_t *out, uint64_t *total, hipStream_t st) {
+    KMAP_TRY(exclusive_scan_u32(in, n, out, st));
+    KMAP_CHECK_HIP(hipMemcpyAsync(total, out + n, 8, hipMemcpyDeviceToHost, st));
+    KMAP_CHECK_HIP(hipStreamSynchronize(st));
+    return KMAP_OK;
+}
 }  // namespace

@@ -200,6 +200,56 @@ def test_counts_large_k_sort_path_vs_oracle(K, O):
     dc.close()
 
 
+SORT_EDGES = (1, 63, 64, 65, 1023, 1024, 1025, 4095, 4096, 4097, 16384, 16385, 20001)
+
+
+def test_sort_path_at_tile_edges(K, O):
+    """run_hashes on hash arrays built here, at the radix sort's own edges: 64 keys are a wave, 1024 a wave's tile, 4096 a block's four
+    tiles, and from 16384 to 16385 keys the pass's scan of 256 x tiles counts goes from the single-block kernel to the tiled one.  k = 17
+    ends in a 2-bit digit, k = 20 on a digit edge, k = 31 runs all eight passes.  Keys come from a pool a third their number (runs),
+    invalid hashes sit at the front, the back and in between (n != nv); at 1025 and 4097 also one key only (a digit group that fills
+    the wave), sorted and descending input."""
+    from kmap_amd import _ffi
+    rng = np.random.default_rng(41)
+    inv = np.uint64(2 ** 64 - 1)
+    dc = K.DeviceCounts()
+
+    def check(valid, h, k):
+        h = np.ascontiguousarray(h, np.uint64)
+        dev = _ffi.DeviceBuffer.from_numpy(h)
+        try:
+            wu, wc = O.count_uniq_hash(valid, k)
+            for merge in (False, True):
+                n_uniq = dc.run_hashes(dev.ptr, len(h), k, merge_revcom=merge)
+                u, c = dc.fetch()
+                ou, oc = O.merge_revcom(wu, wc, k) if merge else (wu, wc)
+                assert n_uniq == len(ou)
+                np.testing.assert_array_equal(u, ou)
+                np.testing.assert_array_equal(c, oc)
+                assert u.dtype == np.uint64 and c.dtype == np.int64
+        finally:
+            dev.free()
+
+    def with_invalid(keys):
+        at = np.sort(rng.integers(0, len(keys) + 1, len(keys) // 7 + 1))
+        return np.concatenate([np.full(2, inv), np.insert(keys, at, inv), np.full(3, inv)])
+
+    for k in (17, 20, 31):
+        for nv in SORT_EDGES:
+            pool = rng.integers(0, 4 ** k, nv // 3 + 1, dtype=np.uint64)
+            keys = pool[rng.integers(0, len(pool), nv)]
+            check(keys, with_invalid(keys), k)
+            if nv in (1025, 4097):
+                check(keys[:1].repeat(nv), with_invalid(keys[:1].repeat(nv)), k)
+                check(keys, with_invalid(np.sort(keys)), k)
+                check(keys, with_invalid(np.sort(keys)[::-1]), k)
+    dev = _ffi.DeviceBuffer.from_numpy(np.full(1500, inv))
+    for merge in (False, True):
+        assert dc.run_hashes(dev.ptr, 1500, 21, merge_revcom=merge) == 0 and dc.n_uniq == 0
+    dev.free()
+    dc.close()
+
+
 def test_counts_random_vs_oracle(K, O):
     rng = np.random.default_rng(21)
     seq, borders = synth_reads(rng, 20000, 20, 160)

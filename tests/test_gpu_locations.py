@@ -182,6 +182,53 @@ def test_two_million_rows_against_numpy(single_chrom):
             np.testing.assert_array_equal(g, w)
 
 
+SORT_EDGES = (1, 63, 64, 65, 1023, 1024, 1025, 4095, 4096, 4097, 16384, 16385, 20001)
+
+
+def _key_bits(bed, seq_ind, pos, L):
+    """the width of the sort key as locations_impl lays it out: name nibbles, end - start, start, chrom rank (one consensus: no bits)"""
+    bits = lambda v: int(v).bit_length()
+    return (4 * len(str(int(seq_ind.max()))) + bits(int(pos.max()) + L) + bits(int(bed.start[seq_ind].max()) + int(pos.max()))
+            + bits(bed.n_chrom - 1))
+
+
+def test_sort_at_tile_edges():
+    """one consensus with one hit in each of M rows, so exactly M sort keys, at the radix sort's own edges (64 keys are a wave, 1024 a
+    wave's tile, 4096 a block's four tiles, past 16384 keys the pass's scan changes kernel).  BED starts from 2^32 up to 2^33,
+    seven-digit seq_ind and 25 chromosomes: the key is wider than 64 bits (asserted), so passes run in its second word.  Once more at
+    4097 keys with one chromosome and one position: whole digits are constant and skipped.  From M = 2 on the last row repeats the
+    first row's seq_ind and position: two keys equal in every field, far apart in the input, whose (equal) triples must come out next
+    to each other, where the numpy model puts them."""
+    from kmap_amd.locations import locate
+    from kmap_amd.reports import Occurrence
+    rng = np.random.default_rng(77)
+    n_bed, L = 2_500_000, 12
+
+    class Bed:
+        pass
+    bed = Bed()
+    bed.n_rows = n_bed
+    bed.start = rng.integers(2 ** 32, 2 ** 33, n_bed).astype(np.int64)
+    ranks = rng.integers(0, 25, n_bed).astype(np.int32)
+    for M, single in [(M, False) for M in SORT_EDGES] + [(4097, True)]:
+        bed.n_chrom = 1 if single else 25
+        bed.chrom_rank = np.zeros(n_bed, np.int32) if single else ranks
+        seq_ind = (1_000_000 + rng.choice(1_500_000, M, replace=False)).astype(np.int64)
+        pos = np.full(M, 57, np.int32) if single else rng.integers(0, 200, M).astype(np.int32)
+        if M > 1:
+            seq_ind[-1], pos[-1] = seq_ind[0], pos[0]
+        assert _key_bits(bed, seq_ind, pos, L) > 64
+        hits = np.ones(M, np.int32)
+        res = locate(bed, Occurrence([hits], [pos], np.full(M, 200), seq_ind), ["A" * L], all_rows=True)
+        want = _numpy_expected(bed.start, bed.chrom_rank, seq_ind, hits, pos, L)
+        assert len(res[0][0]) == M
+        for g, w in zip(res[0], want):
+            np.testing.assert_array_equal(g, w)
+        if M > 1:
+            at = np.flatnonzero(res[0][0] == seq_ind[0])
+            assert len(at) == 2 and at[1] == at[0] + 1
+
+
 def test_in_memory_occurrence_equals_path(tmp_path):
     """an Occurrence, or a scan_motif_occurence-style hit list, in place of the file path: the same files"""
     from kmap_amd.locations import _extract_motif_locations
