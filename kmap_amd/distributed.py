@@ -15,14 +15,22 @@ Sharding: every rank holds all N hashes (<= 1.6 MB) and owns row 
         (rank r owns blocks r, r + world, ...: the upper-triangle work of a block shrinks with its index); a rank's gradient
         buffer then holds partial sums for all points and the all-reduce is a true sum.
     Best-list / early-stop / jitter logic runs redundantly and identically on every rank (apply kernel): no broadcast.
-  * reads (counting, masking, occurrence scan): contiguous read ranges; the 4^k-bin histogram is all-reduced in place,
-    scan hits are all-gathered in read order (padded tensors; device tensors on RCCL).
+  * reads (DistDeviceSeq: counting, masking, occurrence scan): contiguous read ranges for the scans and for counting below
+    k = KEY_SPACE_MIN_K -- the 4^k-bin histogram is all-reduced in place, or reduced slice by slice to the rank that owns the key
+    range -- and scan hits are all-gathered in read order (padded tensors; device tensors on RCCL).  From KEY_SPACE_MIN_K on a
+    multi-rank count is cut by KEY SPACE instead: every rank uploads and masks a copy of ALL reads and counts its key range alone.
 The library launches on the null stream, which is torch's default stream, so collectives are ordered after the kernels that
 produce their operands (and before the ones that consume them) on the device: no host synchronisation brackets them.
 """
+import ctypes as C
 import os
+import threading
 
 import numpy as np
+
+from . import _ffi
+from ._ffi import check
+from .device_seq import DeviceSeq, ScanHits
 
 
 def row_partition(n, world, rank):
@@ -84,7 +92,6 @@ def all_gather_rows_dev(dist, local_dev, n, world, rank, row_elems, group=None):
     rank's device.  RCCL: all_gather of padded device tensors, the result stays in HBM; gloo: staged through the host.
     Returns a DeviceBuffer-like object (`.ptr`, `.free()`)."""
     import torch
-    from . import _ffi
     r0, nr = row_partition(n, world, rank)
     if _coll_device(dist, group) != "cuda":
         rows = local_dev.to_numpy(np.int32, (nr, row_elems)) if nr else np.zeros((0, row_elems), np.int32)
@@ -234,9 +241,7 @@ class PeerExchange:
     is left waiting in a collective) with the handle destroyed.  KMAP_PEER_TIMEOUT_MS: bound of the apply kernel's wait (10 000)."""
 
     def __init__(self, session, n, dist, group=None, _corrupt_handle_of=None):
-        import ctypes as C
         import torch
-        from . import _ffi
         self.s, self.dist, self.group = session, dist, group
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         lib = _ffi.lib()
@@ -306,19 +311,15 @@ class PeerExchange:
         agree(ok, "setting the wait bound (KMAP_PEER_TIMEOUT_MS)")   # doubles as the barrier: nobody pushes before every area is mapped everywhere
 
     def _destroy_now(self):
-        from . import _ffi
         if self._p:
             _ffi.lib().kmap_peer_destroy(self._p)
             self._p = None
 
     def step(self, n_iter):
-        from . import _ffi
         _ffi.check(_ffi.lib().kmap_embed_step_peer(self.s._h, self._p, int(n_iter), None))
 
     def check(self):
         """after a segment: did a wait run into its bound (a peer that never pushed)?  Blocks until the issued iterations ran."""
-        import ctypes as C
-        from . import _ffi
         t, it = _ffi.i32(0), _ffi.i64(0)
         _ffi.check(_ffi.lib().kmap_peer_status(self._p, C.byref(t), C.byref(it)))
         if t.value:
@@ -326,7 +327,6 @@ class PeerExchange:
                               "the coordinates of this run are not to be used")
 
     def close(self):
-        from . import _ffi
         if self._p:
             barrier(self.dist, self.group)        # no rank unmaps an area a peer may still push into
             _ffi.lib().kmap_peer_destroy(self._p)
@@ -413,8 +413,6 @@ def kmap_from_kmers_distributed(samp_kh, samp_cnts, samp_label, conseq_list, kme
     where the validation passes, otherwise the all-reduce + one warning); None = the KMAP_DIST_EXCHANGE environment variable."""
     import torch
     import torch.distributed as dist
-    from . import _ffi
-    from ._ffi import check, ptr
     from .hamdist import hamdist_matrix_dev, pitch_for
     from .kmer_count import get_hash_dtype
     from . import visualization as vz
@@ -521,64 +519,75 @@ def read_partition(borders, world, rank):
     return row_partition(len(borders), world, rank)
 
 
-def _gathered_hits_cls():
-    from .motif_discovery import ScanHits
+def table_bounds(n_bins, world):
+    """the 4^k-bin table cut by key range: rank r owns bins [bounds[r], bounds[r + 1]), every cut a multiple of 8 bins"""
+    return [(n_bins * r // world) & ~7 for r in range(world)] + [n_bins]
 
-    class GatheredHits(ScanHits):
-        """The hit list of ALL reads of a read-sharded scan, gathered by device collectives (RCCL) and still resident in HBM:
-        `parts_hits[r, :reads_of[r]]` / `parts_pos[r, :totals[r]]` are rank r's shard.  Same interface as ScanHits: the summary
-        numbers are known at once, the arrays reach the host on first use (in practice: rank 0's CSV writer thread)."""
 
-        def __init__(self, parts_hits, parts_pos, reads_of, totals, n_reads_hit, max_hits, device):
-            import threading
-            self._ph, self._pp, self._reads_of, self._totals, self._dev = parts_hits, parts_pos, reads_of, totals, device
-            self.n_seq, self.total, self.n_reads_hit, self.max_hits = int(sum(reads_of)), int(sum(totals)), int(n_reads_hit), int(max_hits)
-            self._host, self._owner, self._handle = None, None, None
-            self._lock = threading.Lock()
+def _global_rank(dist, group, r):
+    """rank r of `group` under the name point-to-point style collectives (reduce, gather) want for their dst"""
+    return dist.get_global_rank(group, r) if group is not None else r
 
-        def _cat(self, narrow):
-            import torch
-            with torch.cuda.device(self._dev):          # torch's current device is per thread (CSV writer threads)
-                st = torch.cuda.Stream()                 # own stream: neither waits for nor blocks the launching thread
-                st.wait_stream(torch.cuda.default_stream())
-                with torch.cuda.stream(st):
-                    hits = torch.cat([self._ph[r, :m] for r, m in enumerate(self._reads_of)])
-                    if narrow:
-                        hits = hits.clamp(max=255).to(torch.uint8)
-                    pos = torch.cat([self._pp[r, :m] for r, m in enumerate(self._totals)]) if self.total else torch.zeros(0, dtype=torch.int32)
-                    out = hits.cpu().numpy(), pos.cpu().numpy()
-                st.synchronize()
+
+def _adopt_table(dc, all_u, all_c, k):
+    """the (k-mer, count) device tensors of a whole table -> the table of counts handle dc; returns the number of k-mers"""
+    import torch
+    total = int(all_c.numel())
+    torch.cuda.current_stream().synchronize()                         # adopt copies on the null stream's side of the library
+    check(_ffi.lib().kmap_counts_adopt_dev(dc._h, all_u.data_ptr() if total else None, all_c.data_ptr() if total else None, total, k))
+    dc.k, dc.n_uniq = k, total
+    return total
+
+
+class GatheredHits(ScanHits):
+    """The hit list of ALL reads of a read-sharded scan, gathered by device collectives (RCCL) and still resident in HBM:
+    `parts_hits[r, :reads_of[r]]` / `parts_pos[r, :totals[r]]` are rank r's shard.  Same interface as ScanHits: the summary
+    numbers are known at once, the arrays reach the host on first use (in practice: rank 0's CSV writer thread)."""
+
+    def __init__(self, parts_hits, parts_pos, reads_of, totals, n_reads_hit, max_hits, device):
+        self._ph, self._pp, self._reads_of, self._totals, self._dev = parts_hits, parts_pos, reads_of, totals, device
+        self.n_seq, self.total, self.n_reads_hit, self.max_hits = int(sum(reads_of)), int(sum(totals)), int(n_reads_hit), int(max_hits)
+        self._host, self._owner, self._handle = None, None, None
+        self._lock = threading.Lock()
+
+    def _cat(self, narrow):
+        import torch
+        with torch.cuda.device(self._dev):          # torch's current device is per thread (CSV writer threads)
+            st = torch.cuda.Stream()                 # own stream: neither waits for nor blocks the launching thread
+            st.wait_stream(torch.cuda.default_stream())
+            with torch.cuda.stream(st):
+                hits = torch.cat([self._ph[r, :m] for r, m in enumerate(self._reads_of)])
+                if narrow:
+                    hits = hits.clamp(max=255).to(torch.uint8)
+                pos = torch.cat([self._pp[r, :m] for r, m in enumerate(self._totals)]) if self.total else torch.zeros(0, dtype=torch.int32)
+                out = hits.cpu().numpy(), pos.cpu().numpy()
+            st.synchronize()
+        self._ph = self._pp = None
+        return out
+
+    def host(self):
+        with self._lock:
+            if self._host is None:
+                if self._ph is None:
+                    raise RuntimeError("GatheredHits: the list was already handed to a CSV writer (host_u8)")
+                self._host = list(self._cat(False))
+            return self._host
+
+    @property
+    def unfetched(self):
+        return self._host is None and self._ph is not None
+
+    def host_u8(self):
+        with self._lock:
+            assert self._host is None and self._ph is not None and self.max_hits <= 255
+            return self._cat(True)
+
+    def release(self):
+        """a rank that will never write this list (everyone but the owner of the occurrence files) drops the gathered device
+        tensors at once -- world x (reads + positions) int32 per consensus otherwise stay in HBM until the list object dies;
+        the summary numbers (total, n_reads_hit, max_hits) stay"""
+        with self._lock:
             self._ph = self._pp = None
-            return out
-
-        def host(self):
-            with self._lock:
-                if self._host is None:
-                    if self._ph is None:
-                        raise RuntimeError("GatheredHits: the list was already handed to a CSV writer (host_u8)")
-                    self._host = list(self._cat(False))
-                return self._host
-
-        @property
-        def unfetched(self):
-            return self._host is None and self._ph is not None
-
-        def host_u8(self):
-            with self._lock:
-                assert self._host is None and self._ph is not None and self.max_hits <= 255
-                return self._cat(True)
-
-        def release(self):
-            """a rank that will never write this list (everyone but the owner of the occurrence files) drops the gathered device
-            tensors at once -- world x (reads + positions) int32 per consensus otherwise stay in HBM until the list object dies;
-            the summary numbers (total, n_reads_hit, max_hits) stay"""
-            with self._lock:
-                self._ph = self._pp = None
-
-        def __del__(self):
-            pass
-
-    return GatheredHits
 
 
 KEY_SPACE_MIN_K = 13     # from here on a multi-rank count owns KEY RANGES over all reads instead of read ranges + a table collective
@@ -586,315 +595,327 @@ KEY_SPACE_MIN_K = 13     # from here on a multi-rank count owns KEY RANGES over 
                          # k = 14 2.8 ms against 2.1 ms + an all-reduce of 1 GiB, >= 12 ms on a ring: tools/probes/keyspace_proxy.py)
 
 
-def make_dist_device_seq(seq_np_arr, boarder_mat, dist, group=None, shard_counts=None, key_space=None):
-    """A DeviceSeq holding only this rank's reads whose count()/scan() results are global:
-    count = local histogram -> all-reduce(SUM) of the 4^k uint32 bins -> identical compaction on every rank
-    (k <= 16; per-read dedupe, masking and scanning are local to a read, hence to a rank).  Because every rank then
-    sees the same counts, find_motif(dev_seq=...) makes the same decisions everywhere without further exchange.
-    shard_counts (True / False force it for 11 <= k <= 16; None = for k >= 15 when the reads of all ranks hold fewer than 4^k / 4
-    windows): the bins are owned by key range instead -- every rank receives only the summed counts of ITS slice of the table (one
-    SUM-reduce per slice), compacts that slice, and the (k-mer, count) shards are all-gathered in rank = key order.  Per rank and
-    (G-1)/G: 4^k * 4 B of slices + 4^k B of presence + 12 B per distinct k-mer, against 4^k * 8 B for the all-reduce: it pays while
-    the distinct k-mers number fewer than a quarter of the bins -- and above TOPK_DEVICE_MIN unique k-mers the last term is not paid
-    at all: the table stays sharded (DeviceCounts._shard / CountShard) and find_motif works on local partials.  The reverse-complement merge pairs
-    bins of different slices: it runs BEFORE the reduction on each rank's local table, steered by an all-reduced presence map
-    (half a byte per bin) so that merged(sum over ranks) == sum over ranks(merged); see include/kmap_hip.h.
-    key_space (None = for KEY_SPACE_MIN_K <= k <= 16 on more than one rank; True / False force it for 11 <= k <= 16; KMAP_DIST_KEYSPACE=0 / 1
-    overrides): counting by KEY SPACE -- every rank ALSO holds all packed reads (uploaded on the first such count: 0.625 B / position) and
-    computes positions [4^k r / G, 4^k (r + 1) / G) of the table from the windows that decide them alone
-    (kmap_counts_run_packed_range_dev: a window whose k-mer, or else its reverse complement, lies in the range) -- no table bytes are
-    exchanged at all, and the histogram passes are those of a table 2 / G the size over 2 / G of the windows.  What is exchanged
-    afterwards is what the key-range form exchanges: the shard sizes, and the (k-mer, count) shards only when the table is small
-    enough not to stay sharded (CountShard).  Read-sharded counting all-reduces 4^k x 4 B per count pass (1 GiB at k = 14: >= 12 ms on
-    a ring over xGMI) and its table passes do not shrink with the ranks; masking is replayed on the full copy (a mask pass over all
-    reads per masked consensus, not sharded).
-    scan() returns the hits of ALL reads (all-gathered in read order); `out_n_seq` / `out_read_len` describe the reads those
-    results cover (all of them), `n_seq` / `read_len` stay the local shard the kernels run on.
-    On RCCL the hit lists never pass through the host on their way to the collective: the shards are gathered as device
-    tensors (scan_lazy -> GatheredHits) and only the rank that writes the occurrence file fetches them.
-    The arrays may be views of memory-mapped pickles (kmer_count.load_array_pickle): a rank touches its own slice only."""
-    import ctypes as C
-    import torch
-    from . import _ffi
-    from ._ffi import check
-    from .motif_discovery import TOPK_DEVICE_MIN, DeviceSeq
+def count_form(k, world, n_all_positions, shard_counts, key_space, env=None):
+    """Which of the three forms DistDeviceSeq.count() takes: "all_reduce", "key_range" or "key_space" (see the class).  Depends on
+    nothing that lives on a device: the two constructor arguments, the ranks, all reads' positions and `env`, the value of
+    KMAP_DIST_KEYSPACE ("0" / "1" override key_space; anything else leaves it)."""
+    if k > 16:
+        raise ValueError("sharded counting all-reduces the 4^k histogram and needs k <= 16")
+    ks = key_space
+    if env in ("0", "1"):
+        ks = env == "1"
+    if 11 <= k <= 16 and ((ks is None and k >= KEY_SPACE_MIN_K and world > 1 and shard_counts is None) or ks):
+        return "key_space"
+    by_range = (k >= 15 and 4 * n_all_positions < 4 ** k) if shard_counts is None else bool(shard_counts)
+    if by_range and 11 <= k <= 16 and world <= 15 and (world > 1 or shard_counts):   # one rank: only when forced (tests)
+        return "key_range"
+    return "all_reduce"
 
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    on_dev = _coll_device(dist, group) == "cuda"
-    if on_dev:
-        assert_default_stream()
-    borders = boarder_mat if isinstance(boarder_mat, np.ndarray) and boarder_mat.dtype == np.int64 and boarder_mat.ndim == 2 \
-        else np.ascontiguousarray(boarder_mat, dtype=np.int64).reshape(-1, 2)
-    r0, nr = read_partition(borders, world, rank)
-    if nr:
-        lo, hi = int(borders[r0, 0]), int(borders[r0 + nr - 1, 1]) + 1          # include the last read's separator
-        hi = min(hi, len(seq_np_arr))
-    else:
-        lo = hi = 0
-    local_seq = np.ascontiguousarray(seq_np_arr[lo:hi])
-    local_borders = borders[r0:r0 + nr] - lo
-    reads_of = [read_partition(borders, world, r)[1] for r in range(world)]
-    n_all_positions = len(seq_np_arr)
-    GatheredHits = _gathered_hits_cls() if on_dev else None
 
-    class DistDeviceSeq(DeviceSeq):
-        first_read, n_local_reads, n_all_reads = r0, nr, len(borders)
-        _all_read_len = None
-        keep_sharded = None         # key-range counting: None = keep the table sharded above TOPK_DEVICE_MIN unique k-mers; True / False force it
-        full_table_rank = None      # ... and gather the whole table on this rank as well (the writer of k{k}.pkl)
+class DistDeviceSeq(DeviceSeq):
+    """A DeviceSeq of this rank's reads (a contiguous range, read_partition) whose count() / scan() results are global.  Every rank
+    sees the same counts, so find_motif(dev_seq=...) makes the same decisions everywhere without further exchange.  k <= 16.
+    count() takes one of three forms (count_form()):
 
-        @property
-        def out_read_len(self):
-            """lengths of ALL reads (the reads scan() results cover), computed on first use: only the rank that writes the
-            occurrence file ever asks (160 MB of borders at C3)"""
-            if self._all_read_len is None:
-                self._all_read_len = (borders[:, 1] - borders[:, 0]).astype(np.int64)
-            return self._all_read_len
+    all_reduce: local histogram of the shard -> all-reduce(SUM) of the 4^k uint32 bins -> identical compaction on every rank.  Per-read
+    dedupe and masking are local to a read, hence to a rank.  4^k x 4 B cross the links per count pass (1 GiB at k = 14: >= 12 ms on a
+    ring over xGMI) and the table passes do not shrink with the ranks.
 
-        @out_read_len.setter
-        def out_read_len(self, value):      # DeviceSeq.__init__ assigns the local shard's lengths: not what scan() covers here
-            pass
+    key_range (shard_counts: True / False force it for 11 <= k <= 16; None = for k >= 15 when the reads of all ranks hold fewer than
+    4^k / 4 windows): local histogram of the shard, but the bins are owned by key range (table_bounds) -- every rank receives only the
+    summed counts of ITS slice of the table (one SUM-reduce per slice), compacts that slice, and the (k-mer, count) shards are
+    all-gathered in rank = key order.  Per rank and (G-1)/G: 4^k * 4 B of slices + 4^k B of presence + 12 B per distinct k-mer, against
+    4^k * 8 B for the all-reduce: it pays while the distinct k-mers number fewer than a quarter of the bins -- and above TOPK_DEVICE_MIN
+    unique k-mers the last term is not paid at all: the table stays sharded (DeviceCounts._shard / CountShard) and find_motif works on
+    local partials.  The reverse-complement merge pairs bins of different slices: it runs BEFORE the reduction on each rank's local
+    table, steered by an all-reduced presence map (half a byte per bin) so that merged(sum over ranks) == sum over ranks(merged); see
+    include/kmap_hip.h.
 
-        # masks are LOGGED and applied on demand: to the shard before a read-sharded count of the working mask, to the full copy before
-        # a key-space count -- a k that counts by key space never pays the shard's mask passes, and vice versa
-        _full, _mask_log, _done_shard, _done_full = None, None, 0, 0
+    key_space (key_space: None = for KEY_SPACE_MIN_K <= k <= 16 on more than one rank unless shard_counts is given; True / False force
+    it for 11 <= k <= 16; KMAP_DIST_KEYSPACE=0 / 1 overrides): NOT read-sharded -- every rank also holds ALL packed reads (uploaded on
+    the first such count: 0.625 B / position, the whole input read on every rank) and computes positions [4^k r / G, 4^k (r + 1) / G) of
+    the table from the windows that decide them alone (kmap_counts_run_packed_range_dev: a window whose k-mer, or else its reverse
+    complement, lies in the range).  No table bytes are exchanged at all, and the histogram passes are those of a table 2 / G the size
+    over 2 / G of the windows.  What is exchanged afterwards is what the key-range form exchanges: the shard sizes, and the
+    (k-mer, count) shards only when the table is small enough not to stay sharded.  Masking is replayed on the full copy (a mask pass
+    over all reads per masked consensus, on every rank).
 
-        def _full_seq(self):
-            """all reads, packed, on THIS rank (key-space counting): uploaded on first use; pending masks applied"""
-            if self._full is None:
-                self._full = DeviceSeq(seq_np_arr, borders)
-                self._done_full = 0
-            log = self._mask_log or []
-            for k_, cons_, rad_ in log[self._done_full:]:     # the full copy has the reference's own cross-separator behaviour
-                DeviceSeq.mask(self._full, k_, cons_, rad_)
-            self._done_full = len(log)
-            return self._full
+    Masks are LOGGED by mask() and applied on demand: to the shard before a read-sharded count of the working mask (and before
+    download()), to the full copy before a key-space count -- a k that counts by key space never pays the shard's mask passes, and
+    vice versa.
+    scan() returns the hits of ALL reads (all-gathered in read order); `out_n_seq` / `out_read_len` describe the reads those results
+    cover (all of them), `n_seq` / `read_len` stay the local shard the kernels run on.  On RCCL the hit lists never pass through the
+    host on their way to the collective: the shards are gathered as device tensors (scan_lazy -> GatheredHits) and only the rank that
+    writes the occurrence file fetches them; on gloo (rehearsals) hit lists are exchanged as host tensors and scan_lazy is None.
+    The arrays may be views of memory-mapped pickles (kmer_count.load_array_pickle) and are referenced, not copied: the read-sharded
+    forms and the scans touch this rank's slice only, the first key-space count reads all of them."""
+    keep_sharded = None         # key-range counting: None = keep the table sharded above TOPK_DEVICE_MIN unique k-mers; True / False force it
+    full_table_rank = None      # ... and gather the whole table on this rank as well (the writer of k{k}.pkl)
 
-        def _sync_shard(self):
-            log = self._mask_log or []
-            for k_, cons_, rad_ in log[self._done_shard:]:
-                self._mask_shard(k_, cons_, rad_)
-            self._done_shard = len(log)
+    def __init__(self, seq_np_arr, boarder_mat, dist, group=None, shard_counts=None, key_space=None):
+        self.dist, self.group, self.shard_counts, self.key_space = dist, group, shard_counts, key_space
+        self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
+        self._on_dev = _coll_device(dist, group) == "cuda"
+        if self._on_dev:
+            assert_default_stream()
+        borders = boarder_mat if isinstance(boarder_mat, np.ndarray) and boarder_mat.dtype == np.int64 and boarder_mat.ndim == 2 \
+            else np.ascontiguousarray(boarder_mat, dtype=np.int64).reshape(-1, 2)
+        r0, nr = read_partition(borders, self.world, self.rank)
+        if nr:
+            lo, hi = int(borders[r0, 0]), int(borders[r0 + nr - 1, 1]) + 1          # include the last read's separator
+            hi = min(hi, len(seq_np_arr))
+        else:
+            lo = hi = 0
+        self.first_read, self.n_local_reads, self.n_all_reads = r0, nr, len(borders)
+        self.reads_of = [read_partition(borders, self.world, r)[1] for r in range(self.world)]
+        self.n_all_positions = len(seq_np_arr)
+        self._all_seq, self._all_borders, self._all_read_len = seq_np_arr, borders, None      # references: _full_seq(), out_read_len
+        self._full, self._mask_log, self._done_shard, self._done_full = None, [], 0, 0        # before the base constructor: it calls reset()
+        # gloo rehearsals: hit lists are exchanged as host tensors, no device-resident variant
+        self.scan_lazy = self._scan_gathered if self._on_dev else None
+        super().__init__(np.ascontiguousarray(seq_np_arr[lo:hi]), borders[r0:r0 + nr] - lo)
 
-        def reset(self):
-            DeviceSeq.reset(self)
-            self._mask_log, self._done_shard, self._done_full = [], 0, 0
-            if self._full is not None:
-                self._full.reset()
+    out_n_seq = property(lambda self: self.n_all_reads)
 
-        def close(self):
-            if self._full is not None:
-                self._full.close()
-                self._full = None
-            DeviceSeq.close(self)
+    @property
+    def out_read_len(self):
+        """lengths of ALL reads (the reads scan() results cover), computed on first use: only the rank that writes the
+        occurrence file ever asks (160 MB of borders at C3)"""
+        if self._all_read_len is None:
+            self._all_read_len = (self._all_borders[:, 1] - self._all_borders[:, 0]).astype(np.int64)
+        return self._all_read_len
 
-        def download(self):
+    def _full_seq(self):
+        """all reads, packed, on THIS rank (key-space counting): uploaded on first use; pending masks applied"""
+        if self._full is None:
+            self._full = DeviceSeq(self._all_seq, self._all_borders)
+            self._done_full = 0
+        for k_, cons_, rad_ in self._mask_log[self._done_full:]:     # the full copy has the reference's own cross-separator behaviour
+            DeviceSeq.mask(self._full, k_, cons_, rad_)
+        self._done_full = len(self._mask_log)
+        return self._full
+
+    def _sync_shard(self):
+        for k_, cons_, rad_ in self._mask_log[self._done_shard:]:
+            self._mask_shard(k_, cons_, rad_)
+        self._done_shard = len(self._mask_log)
+
+    def reset(self):
+        DeviceSeq.reset(self)
+        self._mask_log, self._done_shard, self._done_full = [], 0, 0
+        if self._full is not None:
+            self._full.reset()
+
+    def close(self):
+        if self._full is not None:
+            self._full.close()
+            self._full = None
+        DeviceSeq.close(self)
+
+    def download(self):
+        self._sync_shard()
+        return DeviceSeq.download(self)
+
+    def mask(self, k, consensus_kh_arr, max_ham_dist_arr):
+        self._mask_log.append((k, np.array(consensus_kh_arr, dtype=np.uint64), np.array(max_ham_dist_arr, dtype=np.int32)))
+
+    def _mask_shard(self, k, consensus_kh_arr, max_ham_dist_arr):
+        """mask_input on this rank's reads, plus the one effect that crosses a shard boundary: a window that touches a separator
+        has the reference's all-ones hash ("compared like any value", kmer_count.py:580-610), so a consensus within its radius
+        of the all-T k-mer also masks the window that STARTS AT the separator in front of this shard -- on the rank before --
+        and with it the first k - 1 positions here."""
+        DeviceSeq.mask(self, k, consensus_kh_arr, max_ham_dist_arr)
+        if self.first_read == 0 or self.n == 0:
+            return
+        kmask = (1 << (2 * k)) - 1
+        hit = False
+        for c, r in zip(np.asarray(consensus_kh_arr).tolist(), np.asarray(max_ham_dist_arr).tolist()):
+            x = (kmask ^ int(c)) & kmask
+            hit = hit or bin((x | (x >> 1)) & 0x5555555555555555).count("1") <= int(r)
+        if not hit:
+            return
+        # positions [0, min(k - 1, n)) become invalid: a tiny kernel on the stream DeviceSeq.mask's kernels were queued on
+        # (the library's null stream), so it is ordered behind them without a host round trip
+        check(_ffi.lib().kmap_inval_set_prefix_dev(self.inval_work.ptr, min(k - 1, self.n), None))
+
+    def count(self, dc, k, dedupe, merge_revcom, use_work=True, gather_full=False):
+        """gather_full: this call's table is the one k{k}.pkl is written from (find_motif's first round) -- if it stays
+        sharded, rank `full_table_rank` also receives the whole of it.  The masked re-counts of the later rounds never do:
+        12 B per unique k-mer over the links and a second multi-GB table on the writer rank, per round, for nothing."""
+        form = count_form(k, self.world, self.n_all_positions, self.shard_counts, self.key_space, os.environ.get("KMAP_DIST_KEYSPACE"))
+        if self._on_dev:
+            assert_default_stream()
+        if form == "key_space":
+            return self._count_by_key_space(dc, k, dedupe, merge_revcom, use_work, gather_full)
+        bins = self._local_histogram(dc, k, dedupe, use_work)
+        if form == "key_range":
+            return self._count_by_key_range(dc, k, merge_revcom, bins, gather_full)
+        return self._count_by_all_reduce(dc, k, merge_revcom, bins)
+
+    def _local_histogram(self, dc, k, dedupe, use_work):
+        """the 4^k-bin table of this rank's reads in dc; returns it as a device tensor view (int32: its sums wrap like uint32)"""
+        import torch
+        if use_work:
             self._sync_shard()
-            return DeviceSeq.download(self)
+        inval = self.inval_work if use_work else self.inval_orig
+        dc._unshard()
+        check(_ffi.lib().kmap_counts_hist_packed_dev(dc._h, self.codes.ptr, inval.ptr, self.n, self.borders.ptr,
+                                                     self.n_seq, k, int(dedupe), None))
+        p, nb = _ffi.vp(), _ffi.i64(0)
+        check(_ffi.lib().kmap_counts_bins(dc._h, C.byref(p), C.byref(nb)))
+        return torch.as_tensor(_DevArray(p.value, 4 ** k, "<i4"), device="cuda")
 
-        def mask(self, k, consensus_kh_arr, max_ham_dist_arr):
-            if self._mask_log is None:
-                self._mask_log = []
-            self._mask_log.append((k, np.array(consensus_kh_arr, dtype=np.uint64), np.array(max_ham_dist_arr, dtype=np.int32)))
+    def _count_by_all_reduce(self, dc, k, merge_revcom, bins):
+        self.dist.all_reduce(bins, op=self.dist.ReduceOp.SUM, group=self.group)      # stream-ordered after the histogram kernels
+        nu = _ffi.i64(0)
+        check(_ffi.lib().kmap_counts_finish(dc._h, k, int(merge_revcom), C.byref(nu), None))
+        dc.k, dc.n_uniq = k, nu.value
+        return dc.n_uniq
 
-        def _mask_shard(self, k, consensus_kh_arr, max_ham_dist_arr):
-            """mask_input on this rank's reads, plus the one effect that crosses a shard boundary: a window that touches a separator
-            has the reference's all-ones hash ("compared like any value", kmer_count.py:580-610), so a consensus within its radius
-            of the all-T k-mer also masks the window that STARTS AT the separator in front of this shard -- on the rank before --
-            and with it the first k - 1 positions here."""
-            DeviceSeq.mask(self, k, consensus_kh_arr, max_ham_dist_arr)
-            if self.first_read == 0 or self.n == 0:
-                return
-            kmask = (1 << (2 * k)) - 1
-            hit = False
-            for c, r in zip(np.asarray(consensus_kh_arr).tolist(), np.asarray(max_ham_dist_arr).tolist()):
-                x = (kmask ^ int(c)) & kmask
-                hit = hit or bin((x | (x >> 1)) & 0x5555555555555555).count("1") <= int(r)
-            if not hit:
-                return
-            # positions [0, min(k - 1, n)) become invalid: a tiny kernel on the stream DeviceSeq.mask's kernels were queued on
-            # (the library's null stream), so it is ordered behind them without a host round trip
-            check(_ffi.lib().kmap_inval_set_prefix_dev(self.inval_work.ptr, min(k - 1, self.n), None))
+    def _count_by_key_range(self, dc, k, merge_revcom, bins, gather_full=False):
+        """bins: this rank's local 4^k table (device tensor view).  Every collective below works on device tensors (gloo
+        stages them through the host itself)."""
+        import torch
+        dist, group, world, rank = self.dist, self.group, self.world, self.rank
+        lib = _ffi.lib()
+        n_bins = 4 ** k
+        if merge_revcom:
+            nib = torch.empty(n_bins // 2, dtype=torch.uint8, device="cuda")
+            check(lib.kmap_counts_presence_dev(dc._h, k, nib.data_ptr(), None))
+            dist.all_reduce(nib, op=dist.ReduceOp.SUM, group=group)   # <= 15 ranks: a nibble cannot carry
+            check(lib.kmap_counts_merge_presence_dev(dc._h, k, nib.data_ptr(), None))
+            del nib
+        bounds = table_bounds(n_bins, world)
+        works = [dist.reduce(bins[bounds[r]:bounds[r + 1]], dst=_global_rank(dist, group, r), op=dist.ReduceOp.SUM, group=group,
+                             async_op=True) for r in range(world)]
+        for w in works:
+            w.wait()
+        nu = _ffi.i64(0)
+        check(lib.kmap_counts_finish_range(dc._h, k, int(bool(merge_revcom)), bounds[rank], bounds[rank + 1] - bounds[rank],
+                                           C.byref(nu), None))
+        return self._finish_shards(dc, k, nu, gather_full)
 
-        def count(self, dc, k, dedupe, merge_revcom, use_work=True, gather_full=False):
-            """gather_full: this call's table is the one k{k}.pkl is written from (find_motif's first round) -- if it stays
-            sharded, rank `full_table_rank` also receives the whole of it.  The masked re-counts of the later rounds never do:
-            12 B per unique k-mer over the links and a second multi-GB table on the writer rank, per round, for nothing."""
-            if k > 16:
-                raise ValueError("sharded counting all-reduces the 4^k histogram and needs k <= 16")
-            if on_dev:
-                assert_default_stream()
-            ks = key_space
-            if os.environ.get("KMAP_DIST_KEYSPACE") in ("0", "1"):
-                ks = os.environ["KMAP_DIST_KEYSPACE"] == "1"
-            if 11 <= k <= 16 and ((ks is None and k >= KEY_SPACE_MIN_K and world > 1 and shard_counts is None) or ks):
-                return self._count_by_key_space(dc, k, dedupe, merge_revcom, use_work, gather_full)
-            if use_work:
-                self._sync_shard()
-            inval = self.inval_work if use_work else self.inval_orig
-            dc._unshard()
-            check(_ffi.lib().kmap_counts_hist_packed_dev(dc._h, self.codes.ptr, inval.ptr, self.n, self.borders.ptr,
-                                                         self.n_seq, k, int(dedupe), None))
-            p, nb = _ffi.vp(), _ffi.i64(0)
-            check(_ffi.lib().kmap_counts_bins(dc._h, C.byref(p), C.byref(nb)))
-            bins = torch.as_tensor(_DevArray(p.value, 4 ** k, "<i4"), device="cuda")   # int32 sum wraps like uint32
-            by_range = (k >= 15 and 4 * n_all_positions < 4 ** k) if shard_counts is None else bool(shard_counts)
-            if by_range and 11 <= k <= 16 and world <= 15 and (world > 1 or shard_counts):   # one rank: only when forced (tests)
-                return self._count_by_key_range(dc, k, merge_revcom, bins, gather_full)
-            dist.all_reduce(bins, op=dist.ReduceOp.SUM, group=group)      # stream-ordered after the histogram kernels
-            nu = _ffi.i64(0)
-            check(_ffi.lib().kmap_counts_finish(dc._h, k, int(merge_revcom), C.byref(nu), None))
-            dc.k, dc.n_uniq = k, nu.value
-            return dc.n_uniq
+    def _count_by_key_space(self, dc, k, dedupe, merge_revcom, use_work, gather_full):
+        """this rank's key range of the table from ALL reads (no table collective); then the shard bookkeeping of the key-range form"""
+        full = self._full_seq()
+        bounds = table_bounds(4 ** k, self.world)
+        inval = full.inval_work if use_work else full.inval_orig
+        nu = _ffi.i64(0)
+        dc._unshard()
+        check(_ffi.lib().kmap_counts_run_packed_range_dev(dc._h, full.codes.ptr, inval.ptr, full.n, full.borders.ptr, full.n_seq, k,
+                                                          int(dedupe), int(bool(merge_revcom)), bounds[self.rank],
+                                                          bounds[self.rank + 1] - bounds[self.rank], C.byref(nu), None))
+        return self._finish_shards(dc, k, nu, gather_full)
 
-        def _count_by_key_range(self, dc, k, merge_revcom, bins, gather_full=False):
-            """bins: this rank's local 4^k table (device tensor view).  Every collective below works on device tensors (gloo
-            stages them through the host itself)."""
-            lib = _ffi.lib()
-            n_bins = 4 ** k
-            if merge_revcom:
-                nib = torch.empty(n_bins // 2, dtype=torch.uint8, device="cuda")
-                check(lib.kmap_counts_presence_dev(dc._h, k, nib.data_ptr(), None))
-                dist.all_reduce(nib, op=dist.ReduceOp.SUM, group=group)   # <= 15 ranks: a nibble cannot carry
-                check(lib.kmap_counts_merge_presence_dev(dc._h, k, nib.data_ptr(), None))
-                del nib
-            bounds = [(n_bins * r // world) & ~7 for r in range(world)] + [n_bins]
-            owner = [dist.get_global_rank(group, r) if group is not None else r for r in range(world)]
-            works = [dist.reduce(bins[bounds[r]:bounds[r + 1]], dst=owner[r], op=dist.ReduceOp.SUM, group=group, async_op=True)
-                     for r in range(world)]
-            for w in works:
-                w.wait()
-            nu = _ffi.i64(0)
-            check(lib.kmap_counts_finish_range(dc._h, k, int(bool(merge_revcom)), bounds[rank], bounds[rank + 1] - bounds[rank],
-                                               C.byref(nu), None))
-            return self._finish_shards(dc, k, nu, gather_full)
-
-        def _count_by_key_space(self, dc, k, dedupe, merge_revcom, use_work, gather_full):
-            """this rank's key range of the table from ALL reads (no table collective); then the shard bookkeeping of the key-range form"""
-            full = self._full_seq()
-            n_bins = 4 ** k
-            bounds = [(n_bins * r // world) & ~7 for r in range(world)] + [n_bins]
-            inval = full.inval_work if use_work else full.inval_orig
-            nu = _ffi.i64(0)
-            dc._unshard()
-            check(_ffi.lib().kmap_counts_run_packed_range_dev(dc._h, full.codes.ptr, inval.ptr, full.n, full.borders.ptr, full.n_seq, k,
-                                                              int(dedupe), int(bool(merge_revcom)), bounds[rank],
-                                                              bounds[rank + 1] - bounds[rank], C.byref(nu), None))
-            return self._finish_shards(dc, k, nu, gather_full)
-
-        def _finish_shards(self, dc, k, nu, gather_full):
-            """dc holds this rank's shard (nu entries) of a table cut by key range"""
-            lib = _ffi.lib()
-            # the shards, concatenated in rank order, are the table every rank would have compacted from the all-reduced bins
-            sizes = torch.empty(world, dtype=torch.int64, device="cuda")
-            dist.all_gather_into_tensor(sizes, torch.tensor([nu.value], dtype=torch.int64, device="cuda"), group=group)
-            sizes = [int(v) for v in sizes.cpu().numpy()]
-            total = int(sum(sizes))
-            dc._unshard()
-            from . import _policy
-            # KMAP_EXACT / general.exact: find_motif calls np.argpartition on the whole fetched table -> every rank holds it
-            keep = self.keep_sharded if self.keep_sharded is not None else (total > TOPK_DEVICE_MIN and not _policy.exact())
-            if keep:
-                # the table STAYS sharded: find_motif's top-k and Hamming-ball masses are local partials + tiny collectives
-                # (CountShard); only the rank that writes k{k}.pkl -- if any -- receives the other ranks' shards
-                if gather_full and self.full_table_rank is not None:
-                    full = self._gather_table(dc, k, sizes, nu.value, dst=self.full_table_rank)
-                    if full is not None:
-                        dc._full = full
-                dc._shard = CountShard(dist, group, sizes)
-                dc.k, dc.n_uniq = k, total
-                return total
-            all_u, all_c = self._gather_table_tensors(dc, k, sizes, nu.value, dst=None)
-            torch.cuda.current_stream().synchronize()                     # adopt copies on the null stream's side of the library
-            check(lib.kmap_counts_adopt_dev(dc._h, all_u.data_ptr() if total else None, all_c.data_ptr() if total else None, total, k))
+    def _finish_shards(self, dc, k, nu, gather_full):
+        """dc holds this rank's shard (nu entries) of a table cut by key range"""
+        import torch
+        from . import _policy, motif_discovery          # TOPK_DEVICE_MIN is read when used: callers and tests set it on that module
+        # the shards, concatenated in rank order, are the table every rank would have compacted from the all-reduced bins
+        sizes = torch.empty(self.world, dtype=torch.int64, device="cuda")
+        self.dist.all_gather_into_tensor(sizes, torch.tensor([nu.value], dtype=torch.int64, device="cuda"), group=self.group)
+        sizes = [int(v) for v in sizes.cpu().numpy()]
+        total = int(sum(sizes))
+        dc._unshard()
+        # KMAP_EXACT / general.exact: find_motif calls np.argpartition on the whole fetched table -> every rank holds it
+        keep = self.keep_sharded if self.keep_sharded is not None else (total > motif_discovery.TOPK_DEVICE_MIN and not _policy.exact())
+        if keep:
+            # the table STAYS sharded: find_motif's top-k and Hamming-ball masses are local partials + tiny collectives
+            # (CountShard); only the rank that writes k{k}.pkl -- if any -- receives the other ranks' shards
+            if gather_full and self.full_table_rank is not None:
+                full = self._gather_table(dc, k, sizes, nu.value, dst=self.full_table_rank)
+                if full is not None:
+                    dc._full = full
+            dc._shard = CountShard(self.dist, self.group, sizes)
             dc.k, dc.n_uniq = k, total
             return total
+        all_u, all_c = self._gather_table_tensors(dc, k, sizes, nu.value, dst=None)
+        return _adopt_table(dc, all_u, all_c, k)
 
-        def _gather_table_tensors(self, dc, k, sizes, n_mine, dst):
-            """this rank's shard [uniq | cnt] and the others' -> (all_u, all_c) device tensors in key order; dst = None: on every
-            rank (all-gather), else only on rank `dst` (the others return (None, None)).  One padded buffer per rank carries
-            keys and counts together."""
-            lib = _ffi.lib()
-            up, cp, n_tab = _ffi.vp(), _ffi.vp(), _ffi.i64(0)
-            check(lib.kmap_counts_table_dev(dc._h, C.byref(up), C.byref(cp), C.byref(n_tab)))
-            kt, kdt, kw = ("<i4", torch.int32, 1) if k < 16 else ("<i8", torch.int64, 2)       # key width in int32 words
-            cap = max(max(sizes), 1)
-            mine = torch.zeros((kw + 1) * cap, dtype=torch.int32, device="cuda")
-            if n_mine:
-                mine[:kw * n_mine].copy_(torch.as_tensor(_DevArray(up.value, kw * n_mine, "<i4"), device="cuda"))
-                mine[kw * cap:kw * cap + n_mine].copy_(torch.as_tensor(_DevArray(cp.value, n_mine, "<i4"), device="cuda"))
-            if dst is None:
-                flat = torch.empty(world * (kw + 1) * cap, dtype=torch.int32, device="cuda")   # flat: gloo takes no 2-D output
-                dist.all_gather_into_tensor(flat, mine, group=group)
-                parts = flat.view(world, (kw + 1) * cap)
-            else:
-                glist = [torch.empty_like(mine) for _ in range(world)] if rank == dst else None
-                if on_dev:
-                    dist.gather(mine, glist, dst=dist.get_global_rank(group, dst) if group is not None else dst, group=group)
-                else:                                                    # gloo gathers host tensors
-                    hl = [torch.empty(mine.shape, dtype=torch.int32) for _ in range(world)] if rank == dst else None
-                    dist.gather(mine.cpu(), hl, dst=dist.get_global_rank(group, dst) if group is not None else dst, group=group)
-                    if rank == dst:
-                        glist = [t.cuda() for t in hl]
-                if rank != dst:
-                    return None, None
-                parts = glist                                            # indexed per rank below: no stacked copy
-            all_u32 = torch.cat([parts[r][:kw * sizes[r]] for r in range(world)]).contiguous()
-            all_c = torch.cat([parts[r][kw * cap:kw * cap + sizes[r]] for r in range(world)]).contiguous()
-            all_u = all_u32.view(kdt) if kw == 2 else all_u32
-            return all_u, all_c
+    def _gather_table_tensors(self, dc, k, sizes, n_mine, dst):
+        """this rank's shard [uniq | cnt] and the others' -> (all_u, all_c) device tensors in key order; dst = None: on every
+        rank (all-gather), else only on rank `dst` (the others return (None, None)).  One padded buffer per rank carries
+        keys and counts together."""
+        import torch
+        dist, group, world, rank = self.dist, self.group, self.world, self.rank
+        up, cp, n_tab = _ffi.vp(), _ffi.vp(), _ffi.i64(0)
+        check(_ffi.lib().kmap_counts_table_dev(dc._h, C.byref(up), C.byref(cp), C.byref(n_tab)))
+        kdt, kw = (torch.int32, 1) if k < 16 else (torch.int64, 2)                          # key width in int32 words
+        cap = max(max(sizes), 1)
+        mine = torch.zeros((kw + 1) * cap, dtype=torch.int32, device="cuda")
+        if n_mine:
+            mine[:kw * n_mine].copy_(torch.as_tensor(_DevArray(up.value, kw * n_mine, "<i4"), device="cuda"))
+            mine[kw * cap:kw * cap + n_mine].copy_(torch.as_tensor(_DevArray(cp.value, n_mine, "<i4"), device="cuda"))
+        if dst is None:
+            flat = torch.empty(world * (kw + 1) * cap, dtype=torch.int32, device="cuda")   # flat: gloo takes no 2-D output
+            dist.all_gather_into_tensor(flat, mine, group=group)
+            parts = flat.view(world, (kw + 1) * cap)
+        else:
+            glist = [torch.empty_like(mine) for _ in range(world)] if rank == dst else None
+            if self._on_dev:
+                dist.gather(mine, glist, dst=_global_rank(dist, group, dst), group=group)
+            else:                                                    # gloo gathers host tensors
+                hl = [torch.empty(mine.shape, dtype=torch.int32) for _ in range(world)] if rank == dst else None
+                dist.gather(mine.cpu(), hl, dst=_global_rank(dist, group, dst), group=group)
+                if rank == dst:
+                    glist = [t.cuda() for t in hl]
+            if rank != dst:
+                return None, None
+            parts = glist                                            # indexed per rank below: no stacked copy
+        all_u32 = torch.cat([parts[r][:kw * sizes[r]] for r in range(world)]).contiguous()
+        all_c = torch.cat([parts[r][kw * cap:kw * cap + sizes[r]] for r in range(world)]).contiguous()
+        all_u = all_u32.view(kdt) if kw == 2 else all_u32
+        return all_u, all_c
 
-        def _gather_table(self, dc, k, sizes, n_mine, dst):
-            """the whole table as a NEW DeviceCounts on rank dst (None elsewhere)"""
-            from .kmer_count import DeviceCounts
-            all_u, all_c = self._gather_table_tensors(dc, k, sizes, n_mine, dst)
-            if all_u is None:
-                return None
-            full = DeviceCounts()
-            total = int(all_c.numel())
-            torch.cuda.current_stream().synchronize()
-            check(_ffi.lib().kmap_counts_adopt_dev(full._h, all_u.data_ptr() if total else None, all_c.data_ptr() if total else None, total, k))
-            full.k, full.n_uniq = k, total
-            return full
+    def _gather_table(self, dc, k, sizes, n_mine, dst):
+        """the whole table as a NEW DeviceCounts on rank dst (None elsewhere)"""
+        from .kmer_count import DeviceCounts
+        all_u, all_c = self._gather_table_tensors(dc, k, sizes, n_mine, dst)
+        if all_u is None:
+            return None
+        full = DeviceCounts()
+        _adopt_table(full, all_u, all_c, k)
+        return full
 
-        def _scan_gathered(self, k, consensus_kh, radius, revcom):
-            """local scan -> device gather of the shards -> GatheredHits (RCCL only)"""
-            assert_default_stream()
-            lib = _ffi.lib()
-            self._own_scan_handle()
-            tot, nhit, mx = _ffi.i64(0), _ffi.i64(0), _ffi.i32(0)
-            check(lib.kmap_scan_run_packed_dev(self._scan, self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, k,
-                                               int(consensus_kh), int(radius), int(revcom), C.byref(tot), self.planes.ptr, None))
-            check(lib.kmap_scan_summary(self._scan, C.byref(nhit), C.byref(mx), None))
-            hp, pp = _ffi.vp(), _ffi.vp()
-            check(lib.kmap_scan_result_dev(self._scan, C.byref(hp), C.byref(pp), None, None))
-            meta = torch.tensor([tot.value, nhit.value, mx.value], dtype=torch.int64, device="cuda")
-            metas = torch.empty((world, 3), dtype=torch.int64, device="cuda")
-            dist.all_gather_into_tensor(metas, meta, group=group)
-            metas = metas.cpu().numpy()                                  # 24 bytes per rank: the only host hop
-            totals = [int(t) for t in metas[:, 0]]
-            cap_r, cap_p = max(max(reads_of), 1), max(max(totals), 1)
-            mine_h = torch.zeros(cap_r, dtype=torch.int32, device="cuda")
-            if self.n_seq:
-                mine_h[:self.n_seq].copy_(torch.as_tensor(_DevArray(hp.value, self.n_seq, "<i4"), device="cuda"))
-            mine_p = torch.zeros(cap_p, dtype=torch.int32, device="cuda")
-            if tot.value:
-                mine_p[:tot.value].copy_(torch.as_tensor(_DevArray(pp.value, tot.value, "<i4"), device="cuda"))
-            parts_h = torch.empty((world, cap_r), dtype=torch.int32, device="cuda")
-            parts_p = torch.empty((world, cap_p), dtype=torch.int32, device="cuda")
-            dist.all_gather_into_tensor(parts_h, mine_h, group=group)
-            dist.all_gather_into_tensor(parts_p, mine_p, group=group)
-            return GatheredHits(parts_h, parts_p, reads_of, totals, int(metas[:, 1].sum()), int(metas[:, 2].max()), torch.cuda.current_device())
+    def _scan_gathered(self, k, consensus_kh, radius, revcom):
+        """local scan -> device gather of the shards -> GatheredHits (RCCL only)"""
+        import torch
+        assert_default_stream()
+        dist, group, world = self.dist, self.group, self.world
+        lib = _ffi.lib()
+        self._own_scan_handle()
+        tot, nhit, mx = _ffi.i64(0), _ffi.i64(0), _ffi.i32(0)
+        check(lib.kmap_scan_run_packed_dev(self._scan, self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, k,
+                                           int(consensus_kh), int(radius), int(revcom), C.byref(tot), self.planes.ptr, None))
+        check(lib.kmap_scan_summary(self._scan, C.byref(nhit), C.byref(mx), None))
+        hp, pp = _ffi.vp(), _ffi.vp()
+        check(lib.kmap_scan_result_dev(self._scan, C.byref(hp), C.byref(pp), None, None))
+        meta = torch.tensor([tot.value, nhit.value, mx.value], dtype=torch.int64, device="cuda")
+        metas = torch.empty((world, 3), dtype=torch.int64, device="cuda")
+        dist.all_gather_into_tensor(metas, meta, group=group)
+        metas = metas.cpu().numpy()                                  # 24 bytes per rank: the only host hop
+        totals = [int(t) for t in metas[:, 0]]
+        cap_r, cap_p = max(max(self.reads_of), 1), max(max(totals), 1)
+        mine_h = torch.zeros(cap_r, dtype=torch.int32, device="cuda")
+        if self.n_seq:
+            mine_h[:self.n_seq].copy_(torch.as_tensor(_DevArray(hp.value, self.n_seq, "<i4"), device="cuda"))
+        mine_p = torch.zeros(cap_p, dtype=torch.int32, device="cuda")
+        if tot.value:
+            mine_p[:tot.value].copy_(torch.as_tensor(_DevArray(pp.value, tot.value, "<i4"), device="cuda"))
+        parts_h = torch.empty((world, cap_r), dtype=torch.int32, device="cuda")
+        parts_p = torch.empty((world, cap_p), dtype=torch.int32, device="cuda")
+        dist.all_gather_into_tensor(parts_h, mine_h, group=group)
+        dist.all_gather_into_tensor(parts_p, mine_p, group=group)
+        return GatheredHits(parts_h, parts_p, self.reads_of, totals, int(metas[:, 1].sum()), int(metas[:, 2].max()), torch.cuda.current_device())
 
-        def scan(self, k, consensus_kh, radius, revcom):
-            if on_dev:
-                return tuple(self._scan_gathered(k, consensus_kh, radius, revcom).host())
-            hits, pos = DeviceSeq.scan(self, k, consensus_kh, radius, revcom)
-            all_hits = all_gather_concat(dist, hits, reads_of, group)                   # read order = rank order
-            return all_hits, all_gather_concat(dist, pos, None, group)
+    def scan(self, k, consensus_kh, radius, revcom):
+        if self._on_dev:
+            return tuple(self._scan_gathered(k, consensus_kh, radius, revcom).host())
+        hits, pos = DeviceSeq.scan(self, k, consensus_kh, radius, revcom)
+        all_hits = all_gather_concat(self.dist, hits, self.reads_of, self.group)                   # read order = rank order
+        return all_hits, all_gather_concat(self.dist, pos, None, self.group)
 
-    # gloo rehearsals: hit lists are exchanged as host tensors, no device-resident variant
-    DistDeviceSeq.scan_lazy = DistDeviceSeq._scan_gathered if on_dev else None
-    ds = DistDeviceSeq(local_seq, local_borders)
-    ds.out_n_seq = len(borders)
-    return ds
+
+def make_dist_device_seq(seq_np_arr, boarder_mat, dist, group=None, shard_counts=None, key_space=None):
+    """this rank's DistDeviceSeq of the reads; call it on every rank of the group with the same arguments"""
+    return DistDeviceSeq(seq_np_arr, boarder_mat, dist, group, shard_counts, key_space)

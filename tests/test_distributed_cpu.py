@@ -293,3 +293,41 @@ def test_loss_limbs_are_exact_and_order_free():
     for bad in (float("nan"), float("inf"), -1.0, 2.0 ** 47):
         t = loss_to_limbs(bad) + loss_to_limbs(3.0)
         assert np.isnan(loss_from_limbs(t))
+
+
+P, Q = 10 ** 6, 3 * 10 ** 8          # all reads' positions: 4 P < 4^15 <= 4 Q
+COUNT_FORMS = [   # k, world, shard_counts, key_space, KMAP_DIST_KEYSPACE, positions, the form (derived by hand from the rule)
+    (12, 3, None, None, None, P, "all_reduce"),      # below KEY_SPACE_MIN_K, below 15
+    (13, 3, None, None, None, P, "key_space"),       # the default from KEY_SPACE_MIN_K on
+    (13, 1, None, None, None, P, "all_reduce"),      # ... on more than one rank only
+    (15, 1, None, None, None, P, "all_reduce"),      # one rank takes key ranges only when forced
+    (15, 3, None, False, None, P, "key_range"),      # key space refused: k >= 15 with few windows
+    (15, 3, None, False, None, Q, "all_reduce"),     # ... and with many
+    (14, 3, None, None, "0", P, "all_reduce"),       # the switch refuses key space
+    (15, 3, None, None, "0", P, "key_range"),
+    (11, 3, None, None, "1", P, "key_space"),        # the switch forces it from k = 11
+    (11, 3, None, True, None, P, "key_space"),
+    (10, 3, None, True, None, P, "all_reduce"),      # never below k = 11
+    (12, 3, True, None, None, P, "key_range"),       # shard_counts forces key ranges
+    (12, 1, True, None, None, P, "key_range"),       # ... even on one rank
+    (10, 3, True, None, None, P, "all_reduce"),
+    (12, 16, True, None, None, P, "all_reduce"),     # a presence nibble carries at 16 ranks
+    (13, 3, True, None, None, P, "key_range"),       # shard_counts given: the default does not turn to key space
+    (13, 3, True, True, None, P, "key_space"),       # ... an explicit key_space does
+    (13, 3, False, None, None, P, "all_reduce"),
+]
+
+
+@pytest.mark.parametrize("k,world,shard_counts,key_space,env,positions,form", COUNT_FORMS)
+def test_count_form_rule(k, world, shard_counts, key_space, env, positions, form):
+    """which of its three forms a sharded count takes is one pure function of the two constructor arguments, the ranks, k, all reads'
+    positions and KMAP_DIST_KEYSPACE"""
+    from kmap_amd.distributed import KEY_SPACE_MIN_K, count_form
+    assert KEY_SPACE_MIN_K == 13 and 4 * P < 4 ** 15 <= 4 * Q
+    assert count_form(k, world, positions, shard_counts, key_space, env) == form
+
+
+def test_count_form_refuses_k_above_16():
+    from kmap_amd.distributed import count_form
+    with pytest.raises(ValueError, match="k <= 16"):
+        count_form(17, 3, P, None, None, None)

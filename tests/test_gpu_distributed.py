@@ -819,6 +819,68 @@ def test_occurrence_csv_from_read_sharded_seq(tmp_path):
     assert got == want and got.count("\n") > 5000
 
 
+MASK_K = 8
+MASK_CALLS = (("poly_t", [4 ** MASK_K - 1, 0x6C39], [1, 2]),      # TTTTTTTT within radius 1 + an arbitrary 8-mer: the prefix is masked
+              ("far", [0, 0x1B1B], [1, 2]))                       # AAAAAAAA, ACGTACGT: 8 and 6 mismatches from all-T -- it is not
+
+
+def _mask_inputs():
+    """299 reads of 30 positions: read_partition cuts them 100 / 100 / 99, so read 100 -- poly-T like every read r with r % 7 == 2 --
+    opens shard 1 and read 99 -- poly-A like every multiple of 11 -- closes shard 0"""
+    from kmap_amd import synth
+    seq, borders = synth.synth_reads(299, 30, 12)
+    for r in range(0, len(borders), 11):
+        seq[borders[r, 0]:borders[r, 1]] = 0
+    for r in range(2, len(borders), 7):
+        seq[borders[r, 0]:borders[r, 1]] = 3
+    return seq, borders
+
+
+def _mask_worker(rank, world, port, out_dir):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch
+    import torch.distributed as dist
+    from kmap_amd.distributed import make_dist_device_seq
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        seq, borders = _mask_inputs()
+        ds = make_dist_device_seq(seq, borders, dist)
+        r0, nr = ds.first_read, ds.n_local_reads
+        out = {"lohi": np.array([borders[r0, 0], borders[r0 + nr - 1, 1] + 1]), "reads": np.array([r0, nr])}
+        for name, cons, rad in MASK_CALLS:
+            ds.mask(MASK_K, np.array(cons, np.uint64), np.array(rad, np.int32))
+            out[name] = ds.download()
+        np.savez(Path(out_dir) / f"mask_rank{rank}.npz", **out)
+        ds.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_masks_on_read_shards_equal_slices_of_the_one_gpu_mask(tmp_path):
+    """mask() + download() on three read shards (gloo, one GPU) == the same slice of the masked reads of one DeviceSeq, byte for byte,
+    after a mask whose consensus lies within its radius of the all-T k-mer (the window that starts at the separator in front of a
+    shard masks k - 1 = 7 positions into it: kmap_inval_set_prefix_dev) and after a second one far from all-T (which must leave
+    that prefix alone).  k = 8 on 30-position reads: the prefix, the separator and an ordinary window share a 16-position group."""
+    import torch.multiprocessing as mp
+    from kmap_amd.motif_discovery import DeviceSeq
+    mp.spawn(_mask_worker, args=(3, _free_port(), str(tmp_path)), nprocs=3, join=True)
+    res = [np.load(tmp_path / f"mask_rank{r}.npz") for r in range(3)]
+    assert [r["reads"].tolist() for r in res] == [[0, 100], [100, 100], [200, 99]]
+    seq, borders = _mask_inputs()
+    assert (seq[borders[100, 0]:borders[100, 1]] == 3).all() and (seq[borders[99, 0]:borders[99, 1]] == 0).all()
+    ds = DeviceSeq(seq, borders)
+    for name, cons, rad in MASK_CALLS:
+        ds.mask(MASK_K, np.array(cons, np.uint64), np.array(rad, np.int32))
+        want = ds.download()
+        assert (want == 255).sum() > len(borders)                # something beyond the separators is masked
+        for r in res:
+            lo, hi = r["lohi"].tolist()
+            np.testing.assert_array_equal(r[name], want[lo:hi], err_msg=f"{name}: reads {r['reads'].tolist()}")
+    ds.close()
+    assert sorted(r["lohi"].tolist() for r in res) == [[0, 3100], [3100, 6200], [6200, 9269]]
+
+
 def test_scan_motif_cli_under_torchrun(tmp_path):
     """`python -m torch.distributed.run --nproc-per-node 2 -m kmap_amd scan_motif` (reads sharded over two ranks that share
     the test box's GPU, gloo): every output file equals the single-process verb's, a second (cached) run re-uses them."""
