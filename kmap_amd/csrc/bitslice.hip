@@ -4,7 +4,7 @@
 // Used by the occurrence scan (get_motif_occurence, motif_discovery.py:1422-1477 -- BASELINE config C5) and by masking
 // (mask_input, kmer_count.py:580-610), k <= 16.  Both need, per window, only the predicate d <= r (the scan then evaluates the
 // few hit windows exactly to find each read's minimum).  The per-window formulation (scan_nibble_kernel /
-// mask_flag_packed_kernel in packed.hip: alignbit, shift, xor, 2-bit popcount, compare per window and strand: ~21 vector
+// mask_flag_packed_kernel in scan_wide.hip: alignbit, shift, xor, 2-bit popcount, compare per window and strand: ~21 vector
 // instructions per window, VALU-issue bound at 0.85 ms per consensus on the C3 reads) is replaced by:
 //
 //   * bit planes of the reads, built once per upload: planes[2w] = H, planes[2w + 1] = L for the 32 positions of word w (groups
@@ -586,11 +586,7 @@ __device__ __forceinline__ void hr_write(const HrCtx &c, const HrRead &r, uint64
                 }
             }
             const int cnt = __builtin_popcount(keep);
-            int inc = cnt;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int v = __shfl_up(inc, o);
-                if (lane >= o) inc += v;
-            }
+            const int inc = wave_inclusive_scan(cnt);
             uint64_t at = wbase + (uint64_t)(inc - cnt);
             while (keep) {
                 const int tb = 31 - __builtin_clz(keep);
@@ -605,23 +601,6 @@ __device__ __forceinline__ void hr_write(const HrCtx &c, const HrRead &r, uint64
 
 // two-pass form: count kernel (also: the block's hit total) -> exclusive scan of the 1 / 256 as many block totals (caller) ->
 // write kernel (the read's offset = its block's offset + the prefix of the counts inside the block, recomputed from hits[])
-__device__ __forceinline__ unsigned int hr_block_prefix(unsigned int v, unsigned int *s_wave, unsigned int &block_total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned int off = 0;
-    block_total = 0;
-    for (int w = 0; w < HR_TPB / 64; ++w) {
-        if (w < wave) off += s_wave[w];
-        block_total += s_wave[w];
-    }
-    return off + inc - v;                                                  // exclusive prefix of v inside the block
-}
 template <bool WRITE, bool CHECK_INVALID>
 __global__ __launch_bounds__(HR_TPB) void scan_hits_reads_kernel(HrCtx c, const int64_t *__restrict__ borders, int64_t n_seq,
                                                                  int32_t *__restrict__ hits, int8_t *__restrict__ min_dist,
@@ -638,7 +617,7 @@ __global__ __launch_bounds__(HR_TPB) void scan_hits_reads_kernel(HrCtx c, const 
             min_dist[s] = (int8_t)(r.best <= c.radius ? (r.best | (r.mixed ? HR_MIXED : 0)) : -1);
         }
         unsigned int total;
-        (void)hr_block_prefix((unsigned int)r.count, s_wave, total);
+        (void)block_exclusive_scan<HR_TPB / 64>((unsigned int)r.count, s_wave, &total);
         if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
     } else {
         if (s < n_seq) {
@@ -650,8 +629,8 @@ __global__ __launch_bounds__(HR_TPB) void scan_hits_reads_kernel(HrCtx c, const 
                 if (r.mixed) min_dist[s] = (int8_t)r.best;
             }
         }
-        unsigned int total;
-        const unsigned int in_block = hr_block_prefix((unsigned int)r.count, s_wave, total);
+        unsigned int total;                          // unused: asked for because the form with a total sums the lower waves in a fixed-count loop
+        const unsigned int in_block = block_exclusive_scan<HR_TPB / 64>((unsigned int)r.count, s_wave, &total);
         hr_write<CHECK_INVALID>(c, r, block_offs[blockIdx.x] + in_block, pos_out, ~0ull);
     }
 }
@@ -838,7 +817,7 @@ __global__ __launch_bounds__(HR_TPB) void scan_hits_reads_fused_kernel(HrCtx c, 
         min_dist[s] = (int8_t)(r.best <= c.radius ? r.best : -1);
     }
     unsigned int total;
-    const unsigned int in_block = hr_block_prefix((unsigned int)r.count, s_wave, total);
+    const unsigned int in_block = block_exclusive_scan<HR_TPB / 64>((unsigned int)r.count, s_wave, &total);
     if (threadIdx.x == 0) {
         // HF_CURSORS reservation counters, each with its own region of the buffer (a block takes counter blockIdx mod HF_CURSORS):
         // tens of thousands of device-scope fetch-adds on ONE address serialise at the memory side

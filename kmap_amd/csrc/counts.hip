@@ -1,16 +1,16 @@
 // counts.hip -- k-mer counting on device: count_uniq_hash (kmer_count.py:476-491) fused with
-// remove_duplicate_hash_per_seq (:743-760) and merge_revcom (:643-685), the Hamming-ball mass
-// of find_motif (motif_discovery.py:666-673) and the per-read motif occurrence scan
-// (motif_discovery.py:1422-1477).
+// remove_duplicate_hash_per_seq (:743-760) and merge_revcom (:643-685).  Here: the counts handle and the bookkeeping of the
+// device's shared 4^k table, the histograms of a hash ARRAY, the reverse-complement merge and the compaction into (uniq, cnt), and
+// the multi-GPU entry points built on them.  Counting straight from the packed reads: counts_packed.hip; what is read off a finished
+// table (total, top-k, Hamming-ball mass): counts_stats.hip.
 //
 // Counting uses a direct-address histogram of 4^k uint32 bins in HBM for k <= 16 (MI355X has
 // 288 GB: even the 16 GiB table of k = 16 is resident), followed by an order-preserving
 // compaction that applies the reverse-complement merge on the fly.  A uint32 bin wraps exactly
 // like the reference's int64 -> int32 cast of np.unique counts.
 #include <algorithm>
+#include <map>
 #include <mutex>
-#include <type_traits>
-#include <vector>
 
 #include "common.h"
 #include "counts_internal.h"
@@ -74,11 +74,17 @@ constexpr int CT_TILE = BLK * CT_PER_THREAD;   // bins per block
 
 __device__ __forceinline__ uint64_t rc_bits(uint64_t x, int k) { return revcom_hash(x, k); }
 
-// keep/emit decision for bin x (see merge_revcom, kmer_count.py:643-685): returns true if an
-// entry is emitted; key/cnt are the emitted values.
-// merge 3 (key-space-sharded counting, counts_internal.h): `bins` is a rank's range-mode table -- T1 = bins[0, len) holds the counts of
-// the positions lo .. lo + len, T2 = bins[half, half + len) the counts of their reverse complements that lie OUTSIDE the range (a
-// partner inside the range was counted into T1 at its own position).
+// How the compaction applies the reverse-complement merge (merge_revcom, kmer_count.py:643-685).  The kernels take it as an int.
+enum MergeMode : int {
+    MERGE_NONE = 0,       // every non-empty bin is an entry
+    MERGE_GATHER = 1,     // the partner's count is gathered from the WHOLE table, one random read per non-empty bin
+    MERGE_IN_PLACE = 2,   // the table was merged in place beforehand (rc_merge_tiles_kernel): a surviving x > rc(x) had no partner
+    MERGE_KEY_RANGE = 3,  // a rank's range-mode table (counts_internal.h: kmap_key_range): T1 = bins[0, len) holds the counts of the
+                          // positions lo .. lo + len, T2 = bins[half, half + len) those of their reverse complements OUTSIDE the
+                          // range (a partner inside the range was counted into T1 at its own position)
+};
+
+// keep/emit decision for bin x: returns true if an entry is emitted; key/cnt are the emitted values.
 __device__ __forceinline__ bool bin_entry(const uint32_t *__restrict__ bins, uint64_t x, uint32_t c, int k, int merge, uint64_t &key,
                                           uint32_t &cnt, const kmap_key_range &kr = kmap_key_range{}) {
     if (c == 0) return false;
@@ -86,7 +92,7 @@ __device__ __forceinline__ bool bin_entry(const uint32_t *__restrict__ bins, uin
     cnt = c;
     if (!merge) return true;
     const uint64_t r = rc_bits(x, k);
-    if (merge == 3) {
+    if (merge == MERGE_KEY_RANGE) {
         if (r == x) {
             cnt = c + c;
             return true;
@@ -98,7 +104,7 @@ __device__ __forceinline__ bool bin_entry(const uint32_t *__restrict__ bins, uin
         cnt = c + cr;
         return true;
     }
-    if (merge == 2) {   // table already merged in place by rc_merge_tiles_kernel: a surviving x > rc(x) had no partner
+    if (merge == MERGE_IN_PLACE) {
         key = (x > r) ? r : x;
         return true;
     }
@@ -118,7 +124,7 @@ __device__ __forceinline__ bool bin_entry(const uint32_t *__restrict__ bins, uin
 // Split x into (a, m, b) with a / b the top / bottom three bases: rc(x) = (rc3(b), rc(m), rc3(a)), so the 64 x 64 entries
 // that share m pair up with the 64 x 64 entries that share rc(m), transposed.  One block loads both tiles (64 rows of 256
 // contiguous bytes each), merges them through LDS and writes both back in place: bins[x] becomes the merged count of a
-// kept entry, 0 for a deleted or empty one.  The compaction then runs without any gather (merge mode 2).
+// kept entry, 0 for a deleted or empty one.  The compaction then runs without any gather (MERGE_IN_PLACE).
 __device__ __forceinline__ uint32_t rc3(uint32_t v) {   // reverse complement of a 3-base group (6 bits)
     v = 63u - v;
     return ((v & 3u) << 4) | (v & 12u) | (v >> 4);
@@ -229,7 +235,8 @@ __device__ __forceinline__ void load_bins(const uint32_t *__restrict__ bins, uin
 // A block walks CT_TPB consecutive tiles (the per-tile counts / offsets keep their meaning): with one 8-KiB tile per block the
 // 16-GiB table of k = 16 is 2 M blocks and the pass ran at the dispatch rate (2 TB/s), not at the memory's.
 constexpr int CT_TPB = 8;
-// x_base: `bins` is the slice [x_base, x_base + n_bins) of the table (key-range-sharded counting; merge 0 or 2 only: no partner gathers)
+// x_base: `bins` is the slice [x_base, x_base + n_bins) of the table (key-range-sharded counting; MERGE_NONE or MERGE_IN_PLACE: no
+// partner gathers)
 __global__ __launch_bounds__(BLK) void compact_count_kernel(const uint32_t *__restrict__ bins, uint64_t n_bins, int k,
                                                             int merge, uint32_t *__restrict__ block_counts, unsigned n_tiles, uint64_t x_base,
                                                             kmap_key_range kr) {
@@ -251,7 +258,7 @@ __global__ __launch_bounds__(BLK) void compact_count_kernel(const uint32_t *__re
     }
 #pragma unroll
     for (int t = 0; t < CT_TPB; ++t) {
-        for (int o = 32; o > 0; o >>= 1) m[t] += __shfl_down(m[t], o);
+        m[t] = wave_sum(m[t]);
         if ((threadIdx.x & 63) == 0) wsum[t][threadIdx.x >> 6] = m[t];
     }
     __syncthreads();
@@ -286,21 +293,9 @@ __global__ __launch_bounds__(BLK) void compact_write_kernel(const uint32_t *__re
             ++m;
         }
     }
-    // exclusive scan of m across the block: wave scan + wave sums
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = m;
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
     // The tile's entries meet in LDS at their rank inside the tile and leave as contiguous rows.  (Each thread storing its own up to
     // eight entries wrote 4 bytes per lane at a stride of ~4 entries: 16 partly used store instructions per tile; k = 14: 0.63 ms.)
-    const uint32_t local = woff + (inc - m);                              // rank of the thread's first entry inside the tile
-    uint32_t at = local;
+    uint32_t at = block_exclusive_scan<BLK / 64>(m, wsum);                // rank of the thread's first entry inside the tile
 #pragma unroll
     for (int j = 0; j < CT_PER_THREAD; ++j) {
         if (flags & (1u << j)) {
@@ -319,108 +314,6 @@ __global__ __launch_bounds__(BLK) void compact_write_kernel(const uint32_t *__re
     __syncthreads();                                                      // wsum / the staging rows are re-used by the next tile
   }
 }
-
-__global__ __launch_bounds__(BLK) void sum_counts_kernel(const uint32_t *__restrict__ cnt, int64_t n, int as_signed,
-                                                         unsigned long long *__restrict__ total) {
-    // the reference sums int32 counts as Python ints (find_motif :648): sign-extend for k < 16
-    long long s = 0;
-    const int64_t stride = (int64_t)gridDim.x * BLK;
-    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += stride)
-        s += as_signed ? (long long)(int32_t)cnt[i] : (long long)cnt[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if ((threadIdx.x & 63) == 0) atomicAdd(total, (unsigned long long)s);
-}
-
-// ---- top-k by count ---------------------------------------------------------------------------
-// key = (count << 32) | ~index : the maximum key is the largest count, lowest index.  Every thread keeps its own top
-// TK of a grid-strided slice, the block merges them by TK rounds of a block-wide max, the host merges the blocks.
-constexpr int TK = 16;
-__global__ __launch_bounds__(BLK) void topk_kernel(const uint32_t *__restrict__ cnt, int64_t n, int as_signed, int top_k,
-                                                   unsigned long long *__restrict__ out) {
-    __shared__ unsigned long long red[BLK];
-    unsigned long long best[TK];
-#pragma unroll
-    for (int t = 0; t < TK; ++t) best[t] = 0;
-    const int64_t stride = (int64_t)gridDim.x * BLK;
-    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) {
-        const long long cv = as_signed ? (long long)(int32_t)cnt[i] : (long long)cnt[i];
-        if (cv <= 0) continue;
-        unsigned long long key = ((unsigned long long)cv << 32) | (0xFFFFFFFFull - (unsigned long long)i);
-        if (key > best[top_k - 1]) {   // insertion into the descending list
-#pragma unroll
-            for (int t = 0; t < TK; ++t) {
-                if (t < top_k && key > best[t]) {
-                    const unsigned long long tmp = best[t];
-                    best[t] = key;
-                    key = tmp;
-                }
-            }
-        }
-    }
-    int head = 0;
-    for (int round = 0; round < top_k; ++round) {
-        unsigned long long mine = 0;
-#pragma unroll
-        for (int t = 0; t < TK; ++t)
-            if (t == head) mine = best[t];
-        red[threadIdx.x] = (head < top_k) ? mine : 0;
-        __syncthreads();
-        for (int o = BLK / 2; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o && red[threadIdx.x + o] > red[threadIdx.x]) red[threadIdx.x] = red[threadIdx.x + o];
-            __syncthreads();
-        }
-        const unsigned long long win = red[0];
-        __syncthreads();
-        if (threadIdx.x == 0) out[(size_t)blockIdx.x * top_k + round] = win;
-        if (win != 0 && mine == win) ++head;   // keys are unique (they embed the index)
-    }
-}
-
-// ---- Hamming-ball mass -----------------------------------------------------------------------
-struct CandTab {
-    uint64_t fwd[16];
-    uint64_t rc[16];
-    int n;
-};
-template <typename H>
-__global__ __launch_bounds__(BLK) void mass_kernel(const H *__restrict__ uniq, const uint32_t *__restrict__ cnt, int64_t n,
-                                                   int k, CandTab t, int radius, int revcom, int as_signed,
-                                                   unsigned long long *__restrict__ mass) {
-    long long acc[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) acc[c] = 0;
-    const uint64_t m = low_mask<uint64_t>(k);
-    const int64_t stride = (int64_t)gridDim.x * BLK;
-    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) {
-        const uint64_t u = (uint64_t)uniq[i];
-        const long long w = as_signed ? (long long)(int32_t)cnt[i] : (long long)cnt[i];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            if (c < t.n) {
-                int d = popc2((u ^ t.fwd[c]) & m);
-                if (revcom) {
-                    int d2 = popc2((u ^ t.rc[c]) & m);
-                    d = d2 < d ? d2 : d;
-                }
-                if (d <= radius) acc[c] += w;
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < t.n) {   // wave-uniform
-            long long s = acc[c];
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-            if ((threadIdx.x & 63) == 0 && s != 0) atomicAdd(&mass[c], (unsigned long long)s);
-        }
-    }
-}
-
-}  // namespace
-
-#include <map>
-
-namespace {
 
 // The 4^k-bin histogram is transient (one count call, or hist -> all-reduce -> finish in the sharded flow), so all handles of a
 // device share ONE table from the scratch arena instead of owning one each: a fresh handle per k and per find_motif round paid
@@ -481,7 +374,7 @@ int kmap_counts_prepare_bins(kmap_counts *c, int k, hipStream_t st) {
 
 int kmap_counts_reserve_table(kmap_counts *c, size_t entries) {
     if (c->uniq && c->cap >= entries) return KMAP_OK;
-    if (c->uniq) (void)hipFree(c->uniq);
+    if (c->uniq) (void)hipFree(c->uniq);             // the old arrays go first: the table need not fit twice
     if (c->cnt) (void)hipFree(c->cnt);
     c->uniq = nullptr;
     c->cnt = nullptr;
@@ -502,10 +395,13 @@ int kmap_counts_reserve_table(kmap_counts *c, size_t entries) {
     return KMAP_OK;
 }
 
-// order-preserving compaction of the bins [first, first + n_bins) of the table into the handle's uniq/cnt arrays; merge: 0, 1 (partner
-// gathers over the WHOLE table: first must be 0), 2 (table merged in place beforehand)
-static int compact_range(kmap_counts *c, int k, int merge, uint64_t first, uint64_t n_bins, int64_t *n_uniq, hipStream_t st,
-                         bool merge_tiles_first = false, kmap_key_range kr = kmap_key_range{}) {
+// order-preserving compaction of the bins [first, first + n_bins) of the table into the handle's uniq/cnt arrays.  MERGE_GATHER is for the
+// WHOLE table (first = 0); from k = 11 on it is carried out as the in-place merge + MERGE_IN_PLACE (no partner gathers), and the merge
+// counts the survivors per compaction tile as it goes
+static int compact_range(kmap_counts *c, int k, MergeMode merge, uint64_t first, uint64_t n_bins, int64_t *n_uniq, hipStream_t st,
+                         kmap_key_range kr = kmap_key_range{}) {
+    const bool merge_tiles_first = merge == MERGE_GATHER && k >= 11;
+    if (merge_tiles_first) merge = MERGE_IN_PLACE;
     const unsigned nb = grid_for((int64_t)n_bins, CT_TILE);
     uint32_t *bc = nullptr;
     uint64_t *boff = nullptr;
@@ -513,7 +409,7 @@ static int compact_range(kmap_counts *c, int k, int merge, uint64_t first, uint6
     KMAP_TRY(kmap_scratch((void **)&boff, ((size_t)nb + 1) * 8, st, KMAP_SLOT_B));
     const uint32_t *bins = kr.len ? c->bins : c->bins + first;          // a range-mode table (kr) starts at the range's first position
     const unsigned nblk = (nb + CT_TPB - 1) / CT_TPB;
-    if (merge_tiles_first) {   // whole table, k >= 11: merge it in place; the merge counts the survivors per compaction tile as it goes
+    if (merge_tiles_first) {
         KMAP_CHECK_HIP(hipMemsetAsync(bc, 0, (size_t)nb * 4, st));
         rc_merge_tiles_kernel<false><<<(unsigned)((size_t)1 << (2 * (k - 6))), BLK, 0, st>>>(c->bins, k, nullptr, bc);
     } else {
@@ -536,14 +432,12 @@ static int compact_range(kmap_counts *c, int k, int merge, uint64_t first, uint6
 
 // order-preserving compaction of the filled histogram (+ revcom merge) into the handle's uniq/cnt arrays
 int kmap_counts_finish_hist(kmap_counts *c, int k, int merge, int64_t *n_uniq, hipStream_t st) {
-    if (merge == 1 && k >= 11)                 // merge the table in place first; the compaction then needs no partner gathers
-        return compact_range(c, k, 2, 0, (uint64_t)1 << (2 * k), n_uniq, st, true);
-    return compact_range(c, k, merge, 0, (uint64_t)1 << (2 * k), n_uniq, st);
+    return compact_range(c, k, (MergeMode)merge, 0, (uint64_t)1 << (2 * k), n_uniq, st);   // callers pass merge_revcom: 0 or 1
 }
 
 // compaction of a rank's range-mode table (counts_internal.h: kmap_key_range): positions lo .. lo + len in key order
 int kmap_counts_finish_key_range(kmap_counts *c, int k, kmap_key_range r, int64_t *n_uniq, hipStream_t st) {
-    return compact_range(c, k, r.half ? 3 : 0, r.lo, r.len, n_uniq, st, false, r);
+    return compact_range(c, k, r.half ? MERGE_KEY_RANGE : MERGE_NONE, r.lo, r.len, n_uniq, st, r);
 }
 // the whole table is in c->bins: merge it in place (k >= 11), then compact positions [first, first + n_bins)
 int kmap_counts_finish_hist_slice(kmap_counts *c, int k, int merge, uint64_t first, uint64_t n_bins, int64_t *n_uniq, hipStream_t st) {
@@ -551,7 +445,7 @@ int kmap_counts_finish_hist_slice(kmap_counts *c, int k, int merge, uint64_t fir
         KMAP_REQUIRE(k >= 11, "counts: a merged slice needs k >= 11 (k=%d)", k);
         rc_merge_tiles_kernel<false><<<(unsigned)((size_t)1 << (2 * (k - 6))), BLK, 0, st>>>(c->bins, k, nullptr, nullptr);
     }
-    return compact_range(c, k, merge ? 2 : 0, first, n_bins, n_uniq, st);
+    return compact_range(c, k, merge ? MERGE_IN_PLACE : MERGE_NONE, first, n_bins, n_uniq, st);
 }
 
 namespace {
@@ -694,7 +588,7 @@ int kmap_counts_finish_range(kmap_counts *c, int k, int merged, uint64_t first_b
     KMAP_REQUIRE(first_bin + n_bins <= ((uint64_t)1 << (2 * k)) && first_bin % 8 == 0, "counts_finish_range: slice [%llu, +%llu) outside the table or not 8-aligned",
                  (unsigned long long)first_bin, (unsigned long long)n_bins);
     KMAP_TRY(kmap_counts_bins_check(c, "counts_finish_range"));
-    return compact_range(c, k, merged ? 2 : 0, first_bin, n_bins, n_uniq, as_stream(stream));
+    return compact_range(c, k, merged ? MERGE_IN_PLACE : MERGE_NONE, first_bin, n_bins, n_uniq, as_stream(stream));
 }
 /* the handle's table <- device arrays (uint32 / uint64 keys as k < 16 / k >= 16, uint32 counts), copied */
 int kmap_counts_adopt_dev(kmap_counts *c, const void *uniq_dev, const void *cnt_dev, int64_t n_uniq, int k) {
@@ -702,107 +596,23 @@ int kmap_counts_adopt_dev(kmap_counts *c, const void *uniq_dev, const void *cnt_
     KMAP_REQUIRE(n_uniq == 0 || (uniq_dev && cnt_dev), "counts_adopt: null pointer");
     const int narrow = (k < 16);
     if (n_uniq && uniq_dev != c->uniq) {
-        void *u = nullptr;
-        uint32_t *q = nullptr;
-        KMAP_CHECK_HIP(hipMalloc(&u, (size_t)n_uniq * 8));
-        if (hipMalloc((void **)&q, (size_t)n_uniq * 4) != hipSuccess) {
-            (void)hipFree(u);
+        DevBuf u, q;                                  // free the new arrays on every early return, the handle's old ones after the swap
+        KMAP_TRY(u.alloc((size_t)n_uniq * 8));
+        if (q.alloc((size_t)n_uniq * 4) != KMAP_OK) {
             kmap_set_error("counts_adopt: hipMalloc(%zu) failed", (size_t)n_uniq * 4);
             return KMAP_E_NOMEM;
         }
-        hipError_t e = hipMemcpy(u, uniq_dev, (size_t)n_uniq * (narrow ? 4 : 8), hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy(q, cnt_dev, (size_t)n_uniq * 4, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(u);
-            (void)hipFree(q);
-            KMAP_CHECK_HIP(e);
-        }
-        if (c->uniq) KMAP_CHECK_HIP(hipFree(c->uniq));
-        if (c->cnt) KMAP_CHECK_HIP(hipFree(c->cnt));
-        c->uniq = u;
-        c->cnt = q;
+        KMAP_CHECK_HIP(hipMemcpy(u.p, uniq_dev, (size_t)n_uniq * (narrow ? 4 : 8), hipMemcpyDeviceToDevice));
+        KMAP_CHECK_HIP(hipMemcpy(q.p, cnt_dev, (size_t)n_uniq * 4, hipMemcpyDeviceToDevice));
+        std::swap(c->uniq, u.p);
+        void *old_cnt = c->cnt;
+        c->cnt = q.as<uint32_t>();
+        q.p = old_cnt;
         c->cap = (size_t)n_uniq;
     }
     c->k = k;
     c->narrow = narrow;
     c->n_uniq = n_uniq;
-    return KMAP_OK;
-}
-
-int kmap_counts_total(kmap_counts *c, int64_t *total) {
-    KMAP_REQUIRE(c && c->k > 0 && total, "counts_total: nothing counted yet");
-    *total = 0;
-    if (c->n_uniq == 0) return KMAP_OK;
-    DevBuf t;
-    KMAP_TRY(t.alloc(8));
-    KMAP_CHECK_HIP(hipMemset(t.p, 0, 8));
-    int64_t g = (c->n_uniq + BLK - 1) / BLK;
-    if (g > 4096) g = 4096;
-    sum_counts_kernel<<<(unsigned)g, BLK>>>(c->cnt, c->n_uniq, c->narrow, t.as<unsigned long long>());
-    KMAP_CHECK_HIP(hipMemcpy(total, t.p, 8, hipMemcpyDeviceToHost));
-    return KMAP_OK;
-}
-
-int kmap_counts_topk(kmap_counts *c, int top_k, int64_t *idx_out, uint64_t *kh_out, int64_t *cnt_out, int *n_found) {
-    KMAP_REQUIRE(c && c->k > 0, "counts_topk: nothing counted yet");
-    KMAP_REQUIRE(top_k > 0 && top_k <= TK && idx_out && kh_out && cnt_out && n_found, "counts_topk: bad arguments (top_k <= %d)", TK);
-    KMAP_REQUIRE(c->n_uniq < ((int64_t)1 << 32), "counts_topk: more than 2^32 unique k-mers");
-    *n_found = 0;
-    if (c->n_uniq == 0) return KMAP_OK;
-    int64_t g = (c->n_uniq + BLK - 1) / BLK;
-    if (g > 1024) g = 1024;
-    DevBuf out;
-    KMAP_TRY(out.alloc((size_t)g * top_k * 8));
-    topk_kernel<<<(unsigned)g, BLK>>>(c->cnt, c->n_uniq, c->narrow, top_k, out.as<unsigned long long>());
-    KMAP_CHECK_HIP(hipGetLastError());
-    std::vector<unsigned long long> keys((size_t)g * top_k);
-    KMAP_CHECK_HIP(hipMemcpy(keys.data(), out.p, keys.size() * 8, hipMemcpyDeviceToHost));
-    std::sort(keys.begin(), keys.end(), [](unsigned long long a, unsigned long long b) { return a > b; });
-    int m = 0;
-    for (; m < top_k && m < (int)keys.size() && keys[(size_t)m] != 0; ++m) {
-        const int64_t idx = (int64_t)(0xFFFFFFFFull - (keys[(size_t)m] & 0xFFFFFFFFull));
-        idx_out[m] = idx;
-        cnt_out[m] = (int64_t)(keys[(size_t)m] >> 32);
-        if (c->narrow) {
-            uint32_t h = 0;
-            KMAP_CHECK_HIP(hipMemcpy(&h, (const uint32_t *)c->uniq + idx, 4, hipMemcpyDeviceToHost));
-            kh_out[m] = h;
-        } else {
-            KMAP_CHECK_HIP(hipMemcpy(&kh_out[m], (const uint64_t *)c->uniq + idx, 8, hipMemcpyDeviceToHost));
-        }
-    }
-    *n_found = m;
-    return KMAP_OK;
-}
-
-int kmap_counts_hamball_mass(kmap_counts *c, const uint64_t *cands, int n_cand, int radius, int revcom, double *mass_out) {
-    KMAP_REQUIRE(c && c->k > 0, "hamball_mass: nothing counted yet");
-    KMAP_REQUIRE(n_cand >= 0 && (n_cand == 0 || (cands && mass_out)), "hamball_mass: null pointer");
-    DevBuf m;
-    KMAP_TRY(m.alloc(16 * 8));
-    for (int c0 = 0; c0 < n_cand; c0 += 16) {
-        CandTab t;
-        t.n = (n_cand - c0 < 16) ? n_cand - c0 : 16;
-        for (int i = 0; i < t.n; ++i) {
-            t.fwd[i] = cands[c0 + i];
-            t.rc[i] = host_revcom(cands[c0 + i], c->k, c->narrow);
-        }
-        KMAP_CHECK_HIP(hipMemset(m.p, 0, 16 * 8));
-        if (c->n_uniq > 0) {
-            int64_t g = (c->n_uniq + BLK - 1) / BLK;
-            if (g > 2048) g = 2048;
-            if (c->narrow)
-                mass_kernel<uint32_t><<<(unsigned)g, BLK>>>((const uint32_t *)c->uniq, c->cnt, c->n_uniq, c->k, t, radius,
-                                                            revcom, 1, m.as<unsigned long long>());
-            else
-                mass_kernel<uint64_t><<<(unsigned)g, BLK>>>((const uint64_t *)c->uniq, c->cnt, c->n_uniq, c->k, t, radius,
-                                                            revcom, 0, m.as<unsigned long long>());
-            KMAP_CHECK_HIP(hipGetLastError());
-        }
-        long long host[16];
-        KMAP_CHECK_HIP(hipMemcpy(host, m.p, 16 * 8, hipMemcpyDeviceToHost));
-        for (int i = 0; i < t.n; ++i) mass_out[c0 + i] = (double)host[i];
-    }
     return KMAP_OK;
 }
 

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "counts_internal.h"
 #include "packed_keys.h"
+#include "scan_util.h"
 
 namespace {
 constexpr int FC = 8;                                   // XCD classes
@@ -37,7 +38,7 @@ __device__ __forceinline__ void tile_keys(const uint32_t *__restrict__ h, const 
         const int64_t g0 = (t0 >> 4) + (int64_t)GPT * threadIdx.x;
         uint32_t n1;
 #pragma unroll
-        for (int j = 0; j < GPT; ++j) packed_group_keys(h, inval, skip, n, k, g0 + j, *reinterpret_cast<uint32_t(*)[16]>(&v[16 * j]), n1);
+        for (int j = 0; j < GPT; ++j) packed_group_keys(h, inval, skip, n, k, g0 + j, &v[16 * j], n1);
     } else {
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
@@ -70,27 +71,11 @@ __device__ __forceinline__ void raw_pair_load(RawPair &r, const uint32_t *__rest
     r.f23 = f.y;
     r.sk = skip ? skip[g >> 1] : 0u;
 }
-__device__ __forceinline__ void group_keys_from(uint32_t hi, uint32_t lo, uint64_t bad, uint32_t skip16, int64_t left, int k, uint32_t (&keys)[16]) {
-    for (int have = 1; have < k;) {
-        const int step = (have <= k - have) ? have : k - have;
-        bad |= bad << step;
-        have += step;
-    }
-    uint32_t drop16 = ((uint32_t)(bad >> 32) & 0xFFFFu) | skip16;          // windows 0..15 in bits 15..0
-    if (left < 16) drop16 |= left <= 0 ? 0xFFFFu : ((1u << (16 - (int)left)) - 1u);   // windows that start inside the array
-    const int sh = 32 - 2 * k;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const uint32_t top = (i == 0) ? hi : __builtin_amdgcn_alignbit(hi, lo, 32 - 2 * i);
-        keys[i] = (top >> sh) | (uint32_t)__builtin_amdgcn_sbfe((int)drop16, 15 - i, 1);   // all ones when dropped (k <= 14: never a hash)
-    }
-}
 __device__ __forceinline__ void raw_pair_keys(const RawPair &r, int64_t n, int k, int64_t g0, uint32_t (&v)[32]) {
     const uint32_t f0 = r.f01 & 0xFFFFu, f1 = r.f01 >> 16, f2 = r.f23 & 0xFFFFu, f3 = r.f23 >> 16;
-    group_keys_from(r.c0, r.c1, ((uint64_t)f0 << 32) | ((uint64_t)f1 << 16) | f2, r.sk >> 16, n - 16 * g0, k,
-                    *reinterpret_cast<uint32_t(*)[16]>(&v[0]));
-    group_keys_from(r.c1, r.c2, ((uint64_t)f1 << 32) | ((uint64_t)f2 << 16) | f3, r.sk & 0xFFFFu, n - 16 * (g0 + 1), k,
-                    *reinterpret_cast<uint32_t(*)[16]>(&v[16]));
+    uint32_t n1;                                                            // k <= 14: no key is the invalid marker, nothing counted aside
+    group_keys<false>(r.c0, r.c1, ((uint64_t)f0 << 32) | ((uint64_t)f1 << 16) | f2, skip16_in(r.sk, 0), n - 16 * g0, k, &v[0], n1);
+    group_keys<false>(r.c1, r.c2, ((uint64_t)f1 << 32) | ((uint64_t)f2 << 16) | f3, skip16_in(r.sk, 1), n - 16 * (g0 + 1), k, &v[16], n1);
 }
 
 // (1) valid keys per (class, bucket): gcount[class * NB + bucket].  (Measured: a bucket-only extraction -- five instead of eleven
@@ -152,16 +137,7 @@ __global__ __launch_bounds__(FS_TPB) void fine_offsets_kernel(const uint32_t *__
         const int i = i0 + j;
         s += gcb[(size_t)(i % FC) * NB + i / FC];
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = s;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint64_t run = inc - s;
-    for (int w = 0; w < wave; ++w) run += wsum[w];
+    uint64_t run = block_exclusive_scan<FS_TPB / 64>(s, wsum);
     uint64_t size[4] = {0, 0, 0, 0};                                        // keys of the thread's buckets (bpt <= 4)
     for (int j = 0; j < per; ++j) {
         const int i = i0 + j;
@@ -186,19 +162,9 @@ __global__ __launch_bounds__(FS_TPB) void fine_offsets_kernel(const uint32_t *__
         if (size[j] > heavy_min) mine += (((size[j] + slice_len - 1) / slice_len) << 16) + ((uint64_t)1 << 32);
         else mine += 1;
     }
-    uint64_t pinc = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t t = __shfl_up(pinc, o);
-        if (lane >= o) pinc += t;
-    }
     __syncthreads();                                                         // wsum is reused
-    if (lane == 63) wsum[wave] = pinc;
-    __syncthreads();
-    uint64_t before = pinc - mine, all = 0;
-    for (int w = 0; w < FS_TPB / 64; ++w) {
-        if (w < wave) before += wsum[w];
-        all += wsum[w];
-    }
+    uint64_t all;
+    const uint64_t before = block_exclusive_scan<FS_TPB / 64>(mine, wsum, &all);
     const uint32_t n_slices = (uint32_t)(all >> 16) & 0xFFFFu, n_plain = (uint32_t)all & 0xFFFFu, n_heavy = (uint32_t)(all >> 32);
     uint32_t at_plain = n_slices + ((uint32_t)before & 0xFFFFu), at_slice = (uint32_t)(before >> 16) & 0xFFFFu, at_heavy = (uint32_t)(before >> 32);
     uint32_t *items = plan + 4, *heavy = plan + 4 + 2 * NB;
@@ -275,17 +241,9 @@ __global__ __launch_bounds__(FS_TPB) void fine_scatter_kernel(const uint32_t *__
             c[j] = cnt[threadIdx.x * BPT + j];
             s += c[j] + ((c[j] != 0u) << 16);
         }
-        uint32_t inc = s;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wsum[w];
-        uint32_t e = (woff + inc - s) & 0xFFFFu, r = (woff + inc - s) >> 16;
-        if (threadIdx.x == FS_TPB - 1) *total = (woff + inc) & 0xFFFFu;
+        const uint32_t excl = block_exclusive_scan<FS_TPB / 64>(s, wsum);
+        uint32_t e = excl & 0xFFFFu, r = excl >> 16;
+        if (threadIdx.x == FS_TPB - 1) *total = (excl + s) & 0xFFFFu;
         // the buckets' global reservations are issued here and consumed after the placement phase: their round trips (device-scope
         // returning atomics, four per thread at k = 14) hide behind the LDS work instead of standing between two barriers
         unsigned long long g[BPT];
@@ -305,11 +263,7 @@ __global__ __launch_bounds__(FS_TPB) void fine_scatter_kernel(const uint32_t *__
         {   // every wave: popcount prefix over its 64 bitmap words (= the 2048 sorted positions it writes out below)
             const uint32_t bits = startbits[wave * WPW + lane];
             const uint32_t pc = (uint32_t)__builtin_popcount(bits);
-            uint32_t ps = pc;
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t t = __shfl_up(ps, o);
-                if (lane >= o) ps += t;
-            }
+            const uint32_t ps = wave_inclusive_scan(pc);
             pairs[wave * WPW + lane] = make_uint2(bits, ps - pc);
             if (lane == 63) wrank[wave] = ps;
         }

@@ -1,4 +1,6 @@
-// counts_internal.h -- the counts handle shared by counts.hip (histogram path) and counts_sort.hip (k >= 17)
+// counts_internal.h -- the counts handle and what the files of the counting path call of each other: counts.hip (handle, hash-array
+// histograms, merge + compaction), counts_packed.hip (entry points on the packed reads), dedupe_packed.hip, counts_part.hip /
+// counts_fine.hip / counts_range.hip (partitioned histograms, key-range stage), counts_sort.hip (k >= 17), counts_stats.hip
 #pragma once
 #include "common.h"
 
@@ -36,12 +38,16 @@ int kmap_counts_part_hist_u32(kmap_counts *c, const uint32_t *hash_dev, int64_t 
 // the same with the keys hashed on the fly from the 2-bit packed reads (+ per-read dedupe skip bits); adds the all-T 16-mer itself
 int kmap_counts_part_hist_packed(kmap_counts *c, const uint32_t *codes_dev, const uint16_t *inval_dev, const uint32_t *skip_dev,
                                  int64_t n, int k, hipStream_t st);
-// 8 <= k <= 14: the same with 16-bit keys, <= 65 536 bins per bucket and XCD-private bucket streams (counts_fine.hip); hash_dev or
+// 10 <= k <= 14 (kmap_counts_fine_applies): the same with 16-bit keys, <= 65 536 bins per bucket and XCD-private bucket streams (counts_fine.hip); hash_dev or
 // (codes_dev, inval_dev, skip_dev) as above
 bool kmap_counts_fine_applies(int k);
 int kmap_counts_fine_hist(kmap_counts *c, const uint32_t *hash_dev, const uint32_t *codes_dev, const uint16_t *inval_dev,
                           const uint32_t *skip_dev, int64_t n, int k, hipStream_t st);
 int kmap_counts_part_add_bin(kmap_counts *c, size_t bin, const unsigned long long *extra_dev, hipStream_t st);
+// dedupe_packed.hip: skip bits of the per-read de-duplication for k <= 16 (KMAP_SLOT_C; packed_keys.h: skip16_of); *skip_out stays null
+// when a read is too long for the kernel's LDS set or the arrays too short for its prefetch -- the caller then dedupes a hash array
+int dedupe_skip_bits(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, const int64_t *borders_dev, int64_t n_seq, int k,
+                     hipStream_t st, uint32_t **skip_out);
 
 // ---- key-space-sharded counting (multi-GPU, 11 <= k <= 16): every rank holds ALL reads and counts only the windows that decide the
 // entries of ITS key range [lo, lo + len) of the table -- no table collective.  The entry at position y of the merged table

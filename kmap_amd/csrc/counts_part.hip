@@ -112,17 +112,7 @@ __global__ __launch_bounds__(PS_TPB) void part_scatter_kernel(const uint32_t *__
         __syncthreads();
         // exclusive scan of the 1024 counts (one per thread): wave scan + wave sums
         const uint32_t c = cnt[threadIdx.x];
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        uint32_t inc = c;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wsum[w];
-        const uint32_t excl = woff + inc - c;
+        const uint32_t excl = block_exclusive_scan<PS_TPB / 64>(c, wsum);
         __syncthreads();
         loff[threadIdx.x] = excl;
         cnt[threadIdx.x] = excl;                                            // running cursor of the bucket inside the tile
@@ -256,11 +246,7 @@ __global__ __launch_bounds__(PS_TPB) void part2_scatter_kernel(const uint32_t *_
         if (threadIdx.x < 64) {                       // exclusive scan of the S <= 128 counts by the first wave (two per lane)
             const int lane = threadIdx.x;
             const uint32_t c0 = (2 * lane < S) ? cnt[2 * lane] : 0u, c1 = (2 * lane + 1 < S) ? cnt[2 * lane + 1] : 0u;
-            uint32_t inc = c0 + c1;
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t t = __shfl_up(inc, o);
-                if (lane >= o) inc += t;
-            }
+            const uint32_t inc = wave_inclusive_scan(c0 + c1);
             const uint32_t e0 = inc - c0 - c1, e1 = e0 + c0;
             if (2 * lane < S) {
                 loff[2 * lane] = e0;

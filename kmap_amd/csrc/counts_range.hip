@@ -17,6 +17,7 @@
 //     a step's keys may straddle two chunks; a block pads its last chunk with the invalid marker, which the histogram passes skip.
 #include "common.h"
 #include "counts_internal.h"
+#include "packed_keys.h"
 
 namespace {
 constexpr int RS_TPB = 256;                            // four waves: many independent blocks per CU hide each other's barriers
@@ -55,16 +56,8 @@ __global__ __launch_bounds__(RS_TPB) void range_stage_kernel(const uint32_t *__r
         const int64_t g = g0 + threadIdx.x;
         const int64_t gl = g < g_end ? g : g_end - 1;                      // clamped: every lane loads, lanes behind the range keep nothing
         const uint32_t hi = codes[gl], lo = codes[gl + 1];
-        uint64_t bad = ((uint64_t)inval[gl] << 32) | ((uint64_t)inval[gl + 1] << 16) | inval[gl + 2];
-        for (int have = 1; have < k;) {
-            const int step = (have <= k - have) ? have : k - have;
-            bad |= bad << step;
-            have += step;
-        }
-        uint32_t drop16 = (uint32_t)(bad >> 32) & 0xFFFFu;                 // windows 0..15 in bits 15..0
-        if (skip) drop16 |= (skip[gl >> 1] >> ((gl & 1) ? 0 : 16)) & 0xFFFFu;
-        const int64_t left = n - 16 * gl;
-        if (left < 16) drop16 |= left <= 0 ? 0xFFFFu : ((1u << (16 - (int)left)) - 1u);
+        const uint64_t bad = ((uint64_t)inval[gl] << 32) | ((uint64_t)inval[gl + 1] << 16) | inval[gl + 2];
+        uint32_t drop16 = group_drop16(bad, skip16_of(skip, gl), n - 16 * gl, k);   // windows 0..15 in bits 15..0
         if (g >= g_end) drop16 = 0xFFFFu;
         // reverse complement of the 32 bases (hi : lo) as (rhi : rlo): window i's reverse complement is its bits [2 i, 2 i + 2 k)
         const uint32_t rlo = rev_pairs(~hi), rhi = rev_pairs(~lo);

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(PW_TPB) void pwm_hits_kernel(const uint32_t *__rest
         }
         if (g < n_data) hit16[g] = (uint16_t)bits;
         uint32_t cnt = (uint32_t)__builtin_popcount(bits);
-        for (int o = 32; o; o >>= 1) cnt += __shfl_down(cnt, o);
+        cnt = wave_sum(cnt);
         if (lane == 0) tile_cnt[t] = cnt;
     }
 }

@@ -39,12 +39,7 @@ __global__ __launch_bounds__(PW_TPB) void pwm_write_kernel(const uint32_t *__res
         tab, codes, inval, n_data, n_tiles, nch, hit16, tile_cnt, borders, n_seq,
         [&](int64_t t, uint32_t bits, int lane) {      // wave-uniform: the lanes' offsets inside the tile, before any hit is visited
             const uint32_t cnt = (uint32_t)__builtin_popcount(bits);
-            uint32_t inc = cnt;
-            for (int o = 1; o < KMAP_WAVE; o <<= 1) {
-                const uint32_t u = __shfl_up(inc, o);
-                if (lane >= o) inc += u;
-            }
-            out = tile_off[t] + (inc - cnt);
+            out = tile_off[t] + (wave_inclusive_scan(cnt) - cnt);
         },
         [&](int, int64_t p, int64_t, int64_t start, uint64_t, int fwd, int rc) {
             const bool minus = RC && rc > fwd;

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(HB_TPB) void hamball_count_kernel(const H *__restri
 #pragma unroll
     for (int j = 0; j < HB_ITEMS; ++j)
         if (x0 + j < n) m += ball_flags<H>(uniq[x0 + j], c, rc, mask, radius, revcom) & 1u;
-    for (int o = 32; o > 0; o >>= 1) m += __shfl_down(m, o);
+    m = wave_sum(m);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -73,17 +73,7 @@ __global__ __launch_bounds__(HB_TPB) void hamball_write_kernel(const H *__restri
             }
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = m;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    uint64_t pos = block_off[blockIdx.x] + woff + (inc - m);
+    uint64_t pos = block_off[blockIdx.x] + block_exclusive_scan<HB_TPB / 64>(m, wsum);
 #pragma unroll
     for (int j = 0; j < HB_ITEMS; ++j) {
         if (flags & (1u << j)) {

@@ -1,4 +1,5 @@
-// scan_internal.h -- the occurrence-scan handle shared by scan.hip (lists, fetch), packed.hip (Hamming scan) and pwm_scan.hip (PWM scan)
+// scan_internal.h -- the occurrence-scan handle shared by scan.hip (lists, fetch, the Hamming verbs' entry points), bitslice.hip /
+// scan_wide.hip (Hamming scan, k <= 16 / k > 16) and pwm_scan.hip (PWM scan)
 #pragma once
 #include "common.h"
 
@@ -34,3 +35,10 @@ int kmap_bitslice_scan_reads_all(const uint32_t *hit32, const uint32_t *codes, c
                                  int64_t n_seq, int k, uint64_t cons, int revcom, int radius, kmap_scan *s, uint64_t *total_out,
                                  hipStream_t st);
 int kmap_bitslice_declare_uniform(kmap_scan *s, const int64_t *borders, int64_t n_seq, int64_t len, int64_t stride, int *accepted, hipStream_t st);
+
+// scan_wide.hip (k > 16, window by window): the mask's flag passes, 32 consensuses each, on the mask as it is on entry -- pass b's hit
+// bits (uint16 per group) at *hit_out + b * *stride_out (KMAP_SLOT_A), *passes_out passes -- and the whole scan into s (hits, offsets, positions, total)
+int kmap_wide_mask_flags(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, int k, const uint64_t *cons, const int32_t *radius,
+                         int n_cons, uint16_t **hit_out, int64_t *stride_out, int *passes_out, hipStream_t st);
+int kmap_wide_scan_run(kmap_scan *s, const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, const int64_t *borders_dev,
+                       int64_t n_seq, int k, uint64_t c, uint64_t rcc, int radius, int revcom, int64_t *total_hits, hipStream_t st);

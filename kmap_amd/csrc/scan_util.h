@@ -1,8 +1,50 @@
-// scan_util.h -- small shared device utilities: the exclusive scan of uint32 counts (counts*.hip, packed.hip, bitslice.hip, ...)
+// scan_util.h -- small shared device utilities: the scans and sums inside a wave / a block, and the exclusive scan of an array of
+// uint32 counts (counts*.hip, scan_wide.hip, bitslice.hip, ...)
 #pragma once
 #include "common.h"
 
 namespace {
+// ---- inside a wave / a block (1-D blocks of whole waves) ---------------------------------------------------------------------------
+// inclusive prefix sum over the 64 lanes
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_scan(T v) {
+    const int lane = threadIdx.x & 63;
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(v, o);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+// sum over the 64 lanes: lane 0 holds it
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+// exclusive prefix sum of v over the block's WAVES * 64 threads.  wsum: WAVES words of the caller's LDS, the waves' sums after the ONE
+// barrier inside (a caller that scans again through the same words puts a barrier in between); *total: the block's sum, on request.
+// The lower waves are summed by the loop each caller had: to `wave` without a total, a fixed-count predicated one with it (one
+// fixed-count loop for both costs part_scatter_kernel three to five VGPRs)
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T *wsum, T *total = nullptr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const T inc = wave_inclusive_scan(v);
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    T off = 0;
+    if (total) {
+        T all = 0;
+        for (int w = 0; w < WAVES; ++w) {
+            if (w < wave) off += wsum[w];
+            all += wsum[w];
+        }
+        *total = all;
+    } else {
+        for (int w = 0; w < wave; ++w) off += wsum[w];
+    }
+    return off + (inc - v);
+}
+
 // exclusive scan of n uint32 values into uint64 offsets by ONE block (n up to a few million);
 // total written to *total
 __global__ __launch_bounds__(1024) void scan_single_block_kernel(const uint32_t *__restrict__ in, int64_t n,
@@ -45,7 +87,7 @@ __global__ __launch_bounds__(SCAN_TPB) void scan_tile_sums_kernel(const uint32_t
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; ++i)
         if (base + i < n) s += in[base + i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];   // < 2^32 per tile by construction
@@ -62,17 +104,7 @@ __global__ __launch_bounds__(SCAN_TPB) void scan_tiles_kernel(const uint32_t *__
         v[i] = (base + i < n) ? in[base + i] : 0u;
         s += v[i];
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = s;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) ws[wave] = inc;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += ws[w];
-    uint64_t run = tile_off[blockIdx.x] + woff + (inc - s);
+    uint64_t run = tile_off[blockIdx.x] + block_exclusive_scan<SCAN_TPB / 64>(s, ws);
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; ++i) {
         if (base + i < n) out[base + i] = run;

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "scan_util.h"
 
 namespace {
 
@@ -98,13 +99,8 @@ __global__ __launch_bounds__(SH_TPB) void shuffle_starts_kernel(const uint16_t *
         }
         c += (uint32_t)__builtin_popcount(s[j]);
     }
-    uint32_t incl = c;
-    for (int o = 1; o < KMAP_WAVE; o <<= 1) {
-        const uint32_t up = __shfl_up(incl, o);
-        if (lane >= o) incl += up;
-    }
-    if (!WRITE)
-        for (int o = 32; o > 0; o >>= 1) nv += __shfl_down(nv, o);
+    const uint32_t incl = wave_inclusive_scan(c);
+    if (!WRITE) nv = wave_sum(nv);
     if (lane == KMAP_WAVE - 1) wave_starts[wave] = incl;
     if (lane == 0) wave_valid[wave] = nv;
     __syncthreads();

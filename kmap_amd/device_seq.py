@@ -26,7 +26,7 @@ def _as_threshold(t, who):
 
 
 class DeviceSeq:
-    """The encoded reads resident in HBM as 2-bit codes + invalid bitmask (packed.hip), plus the (n_seq, 2) borders.
+    """The encoded reads resident in HBM as 2-bit codes + invalid bitmask (layout: packed.hip), plus the (n_seq, 2) borders.
     `inval_orig` is the pristine mask, `inval_work` the one find_motif masks; the codes are shared."""
 
     def __init__(self, seq_np_arr, boarder_mat, _device_arrays=None):

@@ -1,6 +1,7 @@
-"""GPU parity of the 2-bit-packed read path (packed.hip) against the CPU oracle: pack/unpack round trip, window
-hashes for every k, histogram counting, Hamming-ball masking (incl. the reference's invalid-hash quirk) and the
-occurrence scan.  Bit-exact."""
+"""GPU parity of the 2-bit-packed read path against the CPU oracle: pack/unpack round trip and window hashes for every k
+(packed.hip, packed_keys.h), histogram counting (counts_packed.hip, dedupe_packed.hip, counts_part / _fine / _range.hip),
+Hamming-ball masking (incl. the reference's invalid-hash quirk) and the occurrence scan (scan.hip -> bitslice.hip, scan_wide.hip).
+Bit-exact."""
 import ctypes as C
 
 import numpy as np
@@ -769,6 +770,59 @@ def test_fine_partition_edge_inputs(env, case):
             np.testing.assert_array_equal(c, oc)
     dc.close()
     ds.close()
+
+
+_ENDS_READS = {}
+
+
+def _reads_to_the_last_position(n):
+    """Reads of 20 .. 160 positions with 2 % N that fill exactly n positions: the last read runs to position n - 1 with valid bases
+    and no separator follows it, so windows that start inside the array and run past its end exist.  One array per n, shared by
+    the cases."""
+    if n not in _ENDS_READS:
+        rng = np.random.default_rng(n)
+        seq = np.empty(n, np.uint8)
+        borders, st = [], 0
+        while st < n:
+            left = n - st
+            # the last read takes what is left; the one before it leaves 80 positions
+            L = left if left <= 160 else left - 81 if left <= 181 else int(rng.integers(20, 161))
+            r = rng.integers(0, 4, size=L).astype(np.uint8)
+            r[rng.random(L) < 0.02] = 255
+            if st + L == n:
+                r[-20:] = rng.integers(0, 4, size=20)
+            seq[st:st + L] = r
+            borders.append((st, st + L))
+            if st + L < n:
+                seq[st + L] = 255
+            st += L + 1
+        assert borders[-1][1] == n and borders[-1][1] - borders[-1][0] >= 20 and seq[-1] != 255
+        _ENDS_READS[n] = (seq, np.array(borders, np.int64))
+    return _ENDS_READS[n]
+
+
+@pytest.mark.parametrize("k,n", [(k, n) for k in (1, 7, 8, 9) for n in (65535, 65536, 65553)] +
+                         [(k, n) for k in (10, 14, 15, 16) for n in ((1 << 20) - 1, 1 << 20, (1 << 20) + 32768 + 17)])
+def test_counts_at_array_and_tile_ends(env, k, n):
+    """The tail rule (windows that start at / behind position n are dropped, windows that start inside the array and run past its end
+    are invalid) and the path switches that every counting kernel takes from the shared window-key front end (packed_keys.h):
+    k <= 9 around n = 2^16 (device atomics below, the LDS histograms from there on) with n mod 16 = 15, 0 and 1; k >= 10 around
+    n = 2^20 (the partitioned histograms from there on), the largest n = one full 32 768-window tile + a ragged one.  Counts == oracle,
+    with and without per-read dedupe and reverse-complement merge."""
+    _ffi, DeviceCounts, DeviceSeq, O = env
+    seq, borders = _reads_to_the_last_position(n)
+    ds, dc = DeviceSeq(seq, borders), DeviceCounts()
+    try:
+        for dedupe in (False, True):
+            for merge in (False, True):
+                ds.count(dc, k, dedupe=dedupe, merge_revcom=merge)
+                u, c = dc.fetch()
+                ou, oc = O.count_kmers(seq, borders, k, rep_mode=not dedupe, revcom_mode=merge)
+                np.testing.assert_array_equal(u, ou, err_msg=f"dedupe={dedupe} merge={merge}")
+                np.testing.assert_array_equal(c, oc, err_msg=f"dedupe={dedupe} merge={merge}")
+    finally:
+        dc.close()
+        ds.close()
 
 
 @pytest.mark.parametrize("k", [1, 2, 5, 8, 9, 13, 14, 16])
