@@ -351,10 +351,12 @@ int kmap_pos_density(const int32_t *hits, const int64_t *offs, const int32_t *po
  * label n_cons when the minimum exceeds radius_k; members whose reverse complement is closer are re-oriented IN uniq_dev. */
 int kmap_label_kmers_dev(void *uniq_dev, int64_t n, int k, int n_cons, const uint64_t *cons_kh, const int32_t *cons_len,
                          const int32_t *cons_radius, int radius_k, int revcom_mode, uint8_t *label_dev, void *stream);
-/* per label l < n_labels (<= 64): sum of the counts (np.bincount weights) and number of members; cnt int32 or int64 */
+/* per label l < n_labels (<= 64): sum of the counts (np.bincount weights) and number of members; cnt64 = 0: cnt is int32 (k < 16,
+ * signed like the reference's), 1: int64, 2: the uint32 bins of a resident table with k >= 16 (zero-extended) */
 int kmap_label_sums_dev(const uint8_t *label_dev, const void *cnt_dev, int cnt64, int64_t n, int n_labels, int64_t *weight_sums,
                         int64_t *member_counts);
-/* excl_dev[0..n] (uint64) = exclusive prefix sums of label c's weights (counts; 1 per member if cnt_dev is NULL), [n] = total */
+/* excl_dev[0..n] (uint64) = exclusive prefix sums of label c's weights (counts; 1 per member if cnt_dev is NULL), [n] = total;
+ * cnt64 as above, summed in 64 bits for any n */
 int kmap_label_prefix_dev(const uint8_t *label_dev, const void *cnt_dev, int cnt64, int64_t n, int c, uint32_t *scratch_dev,
                           uint64_t *excl_dev, void *stream);
 /* idx_out[j] = first i whose inclusive prefix exceeds targets[j] (np.searchsorted(cdf, x, "right") on integer weights) */

@@ -3,6 +3,7 @@
 //   * motif position density (reference motif_discovery.py:1255-1327: get_motif_pos_density)
 // Integer results are exact; the density is f64 with the reference's operation order per term (no FMA: the library is
 // built with -ffp-contract=off) and a fixed, chunked summation order over reads.
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -140,14 +141,16 @@ int hamball_extract(const void *uniq_host, const void *cnt_host, int64_t n, int 
     return KMAP_OK;
 }
 
-// the same over the table a counts handle still holds in HBM (uint32 counts whatever k); the members' counts reach the host in the
+// the same over the table a counts handle still holds in HBM (uint32 bins whatever k, read as what they stand for: int32 for k < 16,
+// so that the count matrix sums them as the extraction from host arrays does); the members' counts reach the host in the
 // reference's dtype (int32 for k < 16, int64 otherwise).  cap < members: nothing is written, *n_out says how many there are.
 template <typename H, typename CT>
 int hamball_resident(kmap_counts *c, uint64_t conseq_kh, int radius, int revcom, int64_t cap, void *out_kh, void *out_cnt,
                      int64_t *n_out, int64_t *cnt_mat) {
     DevBuf ou, oc, mat;
     uint64_t total = 0;
-    KMAP_TRY((hamball_core<H, uint32_t>((const H *)c->uniq, c->cnt, c->n_uniq, c->k, conseq_kh, radius, revcom, ou, oc, mat, &total)));
+    using BT = typename std::conditional<sizeof(CT) == 4, int32_t, uint32_t>::type;
+    KMAP_TRY((hamball_core<H, BT>((const H *)c->uniq, (const BT *)c->cnt, c->n_uniq, c->k, conseq_kh, radius, revcom, ou, oc, mat, &total)));
     *n_out = (int64_t)total;
     if ((int64_t)total > cap) return KMAP_OK;
     if (total) {
@@ -398,7 +401,9 @@ int kmap_label_kmers_dev(void *uniq_dev, int64_t n, int k, int n_cons, const uin
     return KMAP_OK;
 }
 
-/* per label l < n_labels (<= 64): sum of the counts and number of members; cnt is int32 (cnt64 = 0) or int64 */
+/* per label l < n_labels (<= 64): sum of the counts and number of members.  cnt64 names the count array: 0 = int32 (k < 16, host
+ * arrays or the resident bins: the reference's int32, bit 31 is the sign), 1 = int64 (k >= 16, host arrays), 2 = uint32 (k >= 16,
+ * the resident bins: zero-extended, so that both k >= 16 forms sum the same unsigned values) */
 int kmap_label_sums_dev(const uint8_t *label_dev, const void *cnt_dev, int cnt64, int64_t n, int n_labels, int64_t *weight_sums,
                         int64_t *member_counts) {
     KMAP_REQUIRE(n >= 0 && n_labels > 0 && n_labels <= 64 && weight_sums && member_counts, "label_sums: bad arguments");
@@ -411,7 +416,9 @@ int kmap_label_sums_dev(const uint8_t *label_dev, const void *cnt_dev, int cnt64
     int64_t g = (n + 255) / 256;
     if (g > 4096) g = 4096;
     unsigned long long *w = acc.as<unsigned long long>();
-    if (cnt64) label_sums_kernel<int64_t><<<(unsigned)g, 256>>>(label_dev, (const int64_t *)cnt_dev, n, n_labels, w, w + 64);
+    KMAP_REQUIRE(cnt64 >= 0 && cnt64 <= 2, "label_sums: cnt64 = %d is none of int32 (0), int64 (1), uint32 (2)", cnt64);
+    if (cnt64 == 1) label_sums_kernel<int64_t><<<(unsigned)g, 256>>>(label_dev, (const int64_t *)cnt_dev, n, n_labels, w, w + 64);
+    else if (cnt64 == 2) label_sums_kernel<uint32_t><<<(unsigned)g, 256>>>(label_dev, (const uint32_t *)cnt_dev, n, n_labels, w, w + 64);
     else label_sums_kernel<int32_t><<<(unsigned)g, 256>>>(label_dev, (const int32_t *)cnt_dev, n, n_labels, w, w + 64);
     KMAP_CHECK_HIP(hipGetLastError());
     unsigned long long host[128];
@@ -424,15 +431,16 @@ int kmap_label_sums_dev(const uint8_t *label_dev, const void *cnt_dev, int cnt64
 }
 
 /* excl_dev[0..n] (uint64) = exclusive prefix sums of the label-c weights (counts, or 1 per member when cnt_dev is NULL);
- * excl_dev[n] = total.  scratch_dev: n uint32. */
+ * excl_dev[n] = total.  scratch_dev: n uint32.  cnt64 as in kmap_label_sums_dev; a weight is the count's low 32 bits, unsigned,
+ * and the prefix is summed in 64 bits whatever n: a tile of k-mer counts may sum past 2^32. */
 int kmap_label_prefix_dev(const uint8_t *label_dev, const void *cnt_dev, int cnt64, int64_t n, int c, uint32_t *scratch_dev,
                           uint64_t *excl_dev, void *stream) {
     KMAP_REQUIRE(n > 0 && label_dev && scratch_dev && excl_dev, "label_prefix: bad arguments");
     hipStream_t st = as_stream(stream);
     const unsigned nb = (unsigned)((n + 255) / 256);
-    if (cnt_dev && cnt64) label_weight_kernel<int64_t><<<nb, 256, 0, st>>>(label_dev, (const int64_t *)cnt_dev, n, c, scratch_dev);
-    else label_weight_kernel<int32_t><<<nb, 256, 0, st>>>(label_dev, (const int32_t *)cnt_dev, n, c, scratch_dev);
-    KMAP_TRY(exclusive_scan_u32(scratch_dev, n, excl_dev, st));
+    if (cnt_dev && cnt64 == 1) label_weight_kernel<int64_t><<<nb, 256, 0, st>>>(label_dev, (const int64_t *)cnt_dev, n, c, scratch_dev);
+    else label_weight_kernel<int32_t><<<nb, 256, 0, st>>>(label_dev, (const int32_t *)cnt_dev, n, c, scratch_dev);   // int32 / uint32: same bits
+    KMAP_TRY(exclusive_scan_u32<uint64_t>(scratch_dev, n, excl_dev, st));
     KMAP_CHECK_HIP(hipGetLastError());
     return KMAP_OK;
 }

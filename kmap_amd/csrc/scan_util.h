@@ -45,9 +45,10 @@ __device__ __forceinline__ T block_exclusive_scan(T v, T *wsum, T *total = nullp
     return off + (inc - v);
 }
 
-// exclusive scan of n uint32 values into uint64 offsets by ONE block (n up to a few million);
+// exclusive scan of n uint32 (IN: or uint64) values into uint64 offsets by ONE block (n up to a few million);
 // total written to *total
-__global__ __launch_bounds__(1024) void scan_single_block_kernel(const uint32_t *__restrict__ in, int64_t n,
+template <typename IN>
+__global__ __launch_bounds__(1024) void scan_single_block_kernel(const IN *__restrict__ in, int64_t n,
                                                                  uint64_t *__restrict__ out,
                                                                  uint64_t *__restrict__ total) {
     __shared__ uint64_t part[1024];
@@ -75,30 +76,36 @@ __global__ __launch_bounds__(1024) void scan_single_block_kernel(const uint32_t 
 
 // ---- multi-block exclusive scan: uint32 in -> uint64 out (+ total) -------------------------------------------
 // phase 1: per-tile sums; phase 2: single-block scan of the tile sums; phase 3: per-tile scan + tile offset.
+// ACC is the type a tile of SCAN_TILE values is summed in.  The contract of uint32_t: every tile sums to less than 2^32 -- flags,
+// per-block and per-bucket counts, whose tile sum is bounded by the number of items behind the tile.  A caller that cannot promise
+// that (k-mer counts: kmap_label_prefix_dev) asks for uint64_t.
 constexpr int SCAN_TPB = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = SCAN_TPB * SCAN_ITEMS;
 
+template <typename ACC>
 __global__ __launch_bounds__(SCAN_TPB) void scan_tile_sums_kernel(const uint32_t *__restrict__ in, int64_t n,
-                                                                  uint32_t *__restrict__ tile_sums) {
-    __shared__ uint32_t ws[SCAN_TPB / 64];
+                                                                  ACC *__restrict__ tile_sums) {
+    __shared__ ACC ws[SCAN_TPB / 64];
     const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t s = 0;
+    ACC s = 0;
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; ++i)
         if (base + i < n) s += in[base + i];
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];   // < 2^32 per tile by construction
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];   // ACC = uint32_t: < 2^32 per tile is the caller's promise
 }
 
+template <typename ACC>
 __global__ __launch_bounds__(SCAN_TPB) void scan_tiles_kernel(const uint32_t *__restrict__ in, int64_t n,
                                                               const uint64_t *__restrict__ tile_off,
                                                               uint64_t *__restrict__ out) {
-    __shared__ uint32_t ws[SCAN_TPB / 64];
+    __shared__ ACC ws[SCAN_TPB / 64];
     const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t v[SCAN_ITEMS], s = 0;
+    uint32_t v[SCAN_ITEMS];
+    ACC s = 0;
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; ++i) {
         v[i] = (base + i < n) ? in[base + i] : 0u;
@@ -112,20 +119,22 @@ __global__ __launch_bounds__(SCAN_TPB) void scan_tiles_kernel(const uint32_t *__
     }
 }
 
-// out[0..n) = exclusive prefix sums of in, out[n] = total.  tile scratch from the arena (slots C and D).
+// out[0..n) = exclusive prefix sums of in, out[n] = total.  tile scratch from the arena (slots C and D).  ACC: see above -- with the
+// default every SCAN_TILE-aligned tile of `in` must sum to less than 2^32 (n <= 4096 is summed in 64 bits either way).
+template <typename ACC = uint32_t>
 inline int exclusive_scan_u32(const uint32_t *in, int64_t n, uint64_t *out, hipStream_t st) {
     if (n <= 4096) {
-        scan_single_block_kernel<<<1, 1024, 0, st>>>(in, n, out, out + n);
+        scan_single_block_kernel<uint32_t><<<1, 1024, 0, st>>>(in, n, out, out + n);
         return KMAP_OK;
     }
     const int64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    uint32_t *tsum = nullptr;
+    ACC *tsum = nullptr;
     uint64_t *toff = nullptr;
-    KMAP_TRY(kmap_scratch((void **)&tsum, (size_t)tiles * 4, st, KMAP_SLOT_C));
+    KMAP_TRY(kmap_scratch((void **)&tsum, (size_t)tiles * sizeof(ACC), st, KMAP_SLOT_C));
     KMAP_TRY(kmap_scratch((void **)&toff, ((size_t)tiles + 1) * 8, st, KMAP_SLOT_D));
-    scan_tile_sums_kernel<<<(unsigned)tiles, SCAN_TPB, 0, st>>>(in, n, tsum);
-    scan_single_block_kernel<<<1, 1024, 0, st>>>(tsum, tiles, toff, out + n);   // total lands in out[n]
-    scan_tiles_kernel<<<(unsigned)tiles, SCAN_TPB, 0, st>>>(in, n, toff, out);
+    scan_tile_sums_kernel<ACC><<<(unsigned)tiles, SCAN_TPB, 0, st>>>(in, n, tsum);
+    scan_single_block_kernel<ACC><<<1, 1024, 0, st>>>(tsum, tiles, toff, out + n);   // total lands in out[n]
+    scan_tiles_kernel<ACC><<<(unsigned)tiles, SCAN_TPB, 0, st>>>(in, n, toff, out);
     return KMAP_OK;
 }
 // the same, then *total = out[n] on the host: returns after st has been synchronised

@@ -493,7 +493,8 @@ class _LabelledTable:
             self.u_d = self._dev(nbytes=max(self.n, 1) * np.dtype(self.hd).itemsize)
             check(_ffi.lib().kmap_memcpy_d2d(self.u_d.ptr, up.value, self.n * np.dtype(self.hd).itemsize, None))
             self.c_d = _ffi.DeviceView(cp.value, self.n * 4, keep=resident)
-            self.cnt64, self.c_dev_dtype = 0, np.uint32                  # device counts are uint32 bins whatever k
+            # device counts are uint32 bins whatever k: int32 bits for k < 16 (0), unsigned for k >= 16 (2: kmap_label_sums_dev)
+            self.cnt64, self.c_dev_dtype = (0 if kmer_len < 16 else 2), np.uint32
         else:
             self.n = len(uniq_kh_arr)
             self.u_d = self._dev(np.ascontiguousarray(uniq_kh_arr, self.hd))
