@@ -283,6 +283,23 @@ int kmap_readscore_packed_dev(const uint32_t *codes_dev, const uint16_t *inval_d
 int kmap_readscore_hist_dev(const int32_t *score_dev, const int32_t *loc_dev, int64_t n_seq, int32_t lo, int64_t n_bins,
                             uint64_t *hist_host, int64_t *n_outside, void *stream);
 
+/* ---- a library of weight matrices against the reads in one call (rank_motif_library; csrc/pwm_library.hip)
+ * -- not in the reference.  For every matrix m (widths[m] columns; weights + 128 m = its [4][32] grid, rows A C G T, columns behind
+ * the width 0) the histogram kmap_readscore_packed_dev + kmap_readscore_hist_dev(lo[m], n_bins[m]) would give, without the per-read
+ * arrays: hist_host holds the matrices' histograms behind one another (sum of n_bins words), n_outside[m] = reads with a valid
+ * window whose best score lies outside [lo[m], lo[m] + n_bins[m]), n_scored[m] = reads with a valid window (it depends on the
+ * width).  The matrices are scored in batches, one pass over the reads per batch, in any order: the results do not depend on it.
+ * Blocking (one synchronisation per batch); integer maxima and counts only, so two calls give the same numbers; scratch memory
+ * only, no handle.  KMAP_E_INVAL: a width outside 4..31, a weight of 2^31 / 31 or more in magnitude (a window's score must fit
+ * int32) or behind the width, a negative size, a NULL array; KMAP_E_UNSUP: more than 2^22 bins for one matrix.  n_mat == 0 writes
+ * nothing; n_seq == 0 or n == 0 gives zeros. */
+int kmap_readscore_library_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
+                               const int64_t *borders_dev, int64_t n_seq,
+                               int n_mat, const int32_t *widths /* host */, const int32_t *weights /* host, n_mat x [4][32] */,
+                               const int32_t *lo /* host */, const int64_t *n_bins /* host */, int revcom,
+                               uint64_t *hist_host, int64_t *n_outside /* host, n_mat */, int64_t *n_scored /* host, n_mat */,
+                               void *stream);
+
 /* ---- k-mer enrichment against a control table (enrich_kmers; csrc/enrich.hip) -- not in the reference.
  * Foreground F: any counts handle (its order is kept; it need not ascend).  Control B: a counts handle counted WITHOUT the
  * reverse-complement merge, keys ascending and unique.  Per foreground entry (x, a): b = B[x] + (revcom ? B[rc x] : 0), a missing key

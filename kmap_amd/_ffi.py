@@ -111,6 +111,7 @@ _SIGS = {
     "kmap_refine_counts_packed_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, i32, i32, i32, vp, P(i64), P(i64), P(i64), vp]),
     "kmap_readscore_packed_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, i32, vp, vp, vp, P(i64), vp]),
     "kmap_readscore_hist_dev": (i32, [vp, vp, i64, i32, i64, vp, P(i64), vp]),
+    "kmap_readscore_library_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "kmap_enrich_create": (i32, [P(vp)]),
     "kmap_enrich_destroy": (i32, [vp]),
     "kmap_enrich_set_control": (i32, [vp, vp, i32, vp]),
@@ -206,7 +207,11 @@ def lib():
                             "(kmap_amd has no CPU fallback)")
         L = C.CDLL(str(LIB_PATH), mode=os.RTLD_GLOBAL if hasattr(os, "RTLD_GLOBAL") else C.DEFAULT_MODE)
         for name, (res, args) in _SIGS.items():
-            f = getattr(L, name)   # AttributeError here = header and library out of sync
+            try:
+                f = getattr(L, name)
+            except AttributeError:     # header and library out of sync: a library built before the symbol was added
+                raise KmapError(f"{LIB_PATH} is out of date, it does not export {name}: run "
+                                "`python -c 'import __graft_entry__ as g; g.build()'`") from None
             f.restype, f.argtypes = res, args
         _lib = L
     return _lib

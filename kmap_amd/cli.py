@@ -3,7 +3,7 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and six verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+figures), and seven verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
 its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
 write, with a strand, a score and a p-value threshold per hit (pwm.py), and `enrich_kmers`, the k-mers and motifs of a result
 directory scored against control reads instead of the uniform null: both read sets counted on the GPU, the tables joined there, a
@@ -11,7 +11,9 @@ pooled two-proportion z per k-mer and an exact top-N selection (enrichment.py), 
 reads -- scan, select, count the selected windows' bases -- until it reproduces itself (refine.py), and `evaluate_pwm`, the best
 window score of every read and of every control read under a count matrix, compared by a rank statistic (AUROC, Mann-Whitney z) and
 by the two-proportion z at every score threshold (evaluate.py), and `shuffle_reads`, the control reads for those two when there is
-no second read set: every read shuffled on the GPU so that its length, its N and its base or dinucleotide counts stay (shuffle.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+no second read set: every read shuffled on the GPU so that its length, its N and its base or dinucleotide counts stay (shuffle.py), and
+`rank_motif_library`, evaluate_pwm's comparison for a whole library of known motifs (MEME text or count matrices) in batched passes
+over the reads, ranked, with Benjamini-Hochberg q-values (library.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -191,6 +193,31 @@ def evaluate_pwm(res_dir, control_fasta_file, matrix_file, p_value=1e-4, min_sco
     from .evaluate import _evaluate_pwm
     _evaluate_pwm(res_dir, control_fasta_file, list(matrix_file), p_value, min_score, pseudocount, revcom_mode, min_reads, read_scores,
                   output_dir)
+
+
+@cli.command(name="rank_motif_library")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--control_fasta_file", type=str, required=True,
+              help="FASTA file of the control reads (input DNA, flanks, round 0, shuffled reads); scored like the reads of res_dir")
+@click.option("--library_file", type=str, required=True, multiple=True,
+              help="motif library: a MEME minimal text file, a 4 x w base-count matrix CSV (as for evaluate_pwm), or a directory of "
+                   "*.meme and *.csv files; may be given several times")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="the reads above scan_pwm's threshold of this p-value are compared too (per strand and per position)")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base)")
+@click.option("--nsites_default", type=int, default=20, required=False,
+              help="sites behind a MEME motif without nsites= (its probabilities become counts of this many sites)")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="score both strands and keep the better one (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--min_reads", type=int, default=10, required=False,
+              help="the best threshold is sought among those that at least this many reads (of both sets together) reach")
+@click.option("--top_hist", type=int, default=0, required=False, help="also write the score histograms of this many best-ranked motifs")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: pwm_library in res_dir)")
+def rank_motif_library(res_dir, control_fasta_file, library_file, p_value=1e-4, pseudocount=1.0, nsites_default=20, revcom_mode=None,
+                       min_reads=10, top_hist=0, output_dir=None):
+    from .library import _rank_motif_library
+    _rank_motif_library(res_dir, control_fasta_file, list(library_file), p_value, pseudocount, nsites_default, revcom_mode, min_reads,
+                        top_hist, output_dir)
 
 
 @cli.command(name="shuffle_reads")

@@ -1,7 +1,8 @@
-// pwm_internal.h -- what pwm_scan.hip (scan_pwm), pwm_refine.hip (refine_pwm) and pwm_readscore.hip (evaluate_pwm) share; DESIGN.md
-// sections 11, 13 and 14.
+// pwm_internal.h -- what pwm_scan.hip (scan_pwm), pwm_refine.hip (refine_pwm), pwm_readscore.hip (evaluate_pwm) and pwm_library.hip
+// (rank_motif_library) share; DESIGN.md sections 11, 13, 14 and 16.
 //   device: the chunk tables, the group loads, the window helpers, pass A (pwm_hits_kernel: hit bit per position + hit count per wave
-//           tile) and for_each_hit, the ONE sparse traversal of pass A's hits that every later pass of scan and refine is a call of
+//           tile), for_each_hit, the ONE sparse traversal of pass A's hits that every later pass of scan and refine is a call of,
+//           and tile_read_starts, the reads of a wave tile for the two dense per-read passes
 //   host:   PwmPlan (an entry point's checks, the weights as a kernel argument, the launch geometry), pwm_pass_a (scratch, launch,
 //           exclusive scan of the tile counts, total) and with_bool (a run-time flag as a template argument)
 #pragma once
@@ -131,6 +132,68 @@ __device__ __forceinline__ int64_t find_read(const int64_t *__restrict__ borders
         if (borders[2 * mid] <= p) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// ---- the reads of a wave tile: what the dense per-read passes share (pwm_readscore.hip, pwm_library.hip) -----------------------------
+constexpr int RS_TILE_POS = PW_TILE_GROUPS * 16;      // 1024 positions per wave tile
+
+// the wave's own LDS words: what its lanes wrote (stores, atomics) before is what they read after; no block barrier -- the waves of
+// a block run different numbers of tiles
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the number of reads that start before array position p (the borders ascend); the whole wave calls it with the same p and gets
+// the same answer
+__device__ __forceinline__ int64_t reads_before(const int64_t *__restrict__ borders, int64_t n_seq, int64_t p, int lane) {
+    int64_t lo = 0, hi = n_seq;            // reads below lo start before p, reads from hi on do not
+    while (lo < hi) {
+        const int64_t step = (hi - lo + KMAP_WAVE - 1) / KMAP_WAVE, idx = lo + lane * step;
+        const bool before = idx < hi && borders[2 * idx] < p;
+        const int c = __builtin_popcountll(__ballot(before));      // the answers are 1 .. 1 0 .. 0
+        if (c == 0) break;
+        if (lo + c * step < hi) hi = lo + c * step;
+        lo = lo + (c - 1) * step + 1;
+    }
+    return lo;
+}
+
+// The read starts of the wave tile that begins at array position tile0, found once per tile by the whole wave: `base` reads start
+// before the tile, those from base on are marked where they start in the wave's 64 LDS words bits / cnt (per group of the tile: one
+// bit per position, position 0 in bit 15, and how many reads start there -- reads may share a start).  The lane gets its group's
+// words (sb, sc) and returns the last read that starts before its group's first position (-1: none).
+__device__ __forceinline__ int64_t tile_read_starts(const int64_t *__restrict__ borders, int64_t n_seq, int64_t tile0, int lane,
+                                                    uint32_t *bits, uint32_t *cnt, uint32_t &sb, uint32_t &sc) {
+    const int64_t base = reads_before(borders, n_seq, tile0, lane);
+    bits[lane] = 0;
+    cnt[lane] = 0;
+    wave_lds_sync();
+    for (int64_t r = base + lane;; r += KMAP_WAVE) {
+        const int64_t rel = r < n_seq ? borders[2 * r] - tile0 : (int64_t)RS_TILE_POS;
+        const bool in = rel >= 0 && rel < RS_TILE_POS;
+        if (in) {
+            atomicOr(&bits[rel >> 4], 0x8000u >> (rel & 15));
+            atomicAdd(&cnt[rel >> 4], 1u);
+        }
+        if (__ballot(in) != ~0ull) break;          // uniform: the starts ascend
+    }
+    wave_lds_sync();
+    sb = bits[lane];
+    sc = cnt[lane];
+    uint32_t before = sc;                          // reads that start in the tile before this lane's group
+    for (int o = 1; o < KMAP_WAVE; o <<= 1) {
+        const uint32_t up = __shfl_up(before, o);
+        if (lane >= o) before += up;
+    }
+    before -= sc;
+    return base + (int64_t)before - 1;
+}
+// a read starts at position i of the lane's group: r moves to the last read that starts there
+__device__ __forceinline__ void step_read(const int64_t *__restrict__ borders, int64_t n_seq, int64_t p, bool shared_starts, int64_t &r) {
+    if (r + 1 < n_seq) ++r;
+    while (shared_starts && r + 1 < n_seq && borders[2 * (r + 1)] <= p) ++r;
 }
 
 // The sparse traversal of pass A's hits, in array order per lane: the block's waves stride over the tiles with hits, a lane takes the

@@ -23,36 +23,12 @@
 
 namespace {
 
-constexpr int RS_TILE_POS = PW_TILE_GROUPS * 16;      // 1024 positions per wave tile
 constexpr int RS_LDS_BINS = 4096;                     // histogram ranges up to this many bins are privatised per block
 constexpr int RS_HIST_BLOCKS = 1024;
 constexpr int64_t RS_MAX_BINS = 1ll << 22;
 
 __device__ __forceinline__ uint64_t pack_read_key(int score, uint32_t loc, bool minus) {
     return ((uint64_t)((uint32_t)score ^ 0x80000000u) << 32) | ((uint64_t)(0x7FFFFFFFu - loc) << 1) | (minus ? 1u : 0u);
-}
-
-// the wave's own LDS words: what its lanes wrote (stores, atomics) before is what they read after; no block barrier -- the waves of
-// a block run different numbers of tiles
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the number of reads that start before array position p (the borders ascend); the whole wave calls it with the same p and gets
-// the same answer
-__device__ __forceinline__ int64_t reads_before(const int64_t *__restrict__ borders, int64_t n_seq, int64_t p, int lane) {
-    int64_t lo = 0, hi = n_seq;            // reads below lo start before p, reads from hi on do not
-    while (lo < hi) {
-        const int64_t step = (hi - lo + KMAP_WAVE - 1) / KMAP_WAVE, idx = lo + lane * step;
-        const bool before = idx < hi && borders[2 * idx] < p;
-        const int c = __builtin_popcountll(__ballot(before));      // the answers are 1 .. 1 0 .. 0
-        if (c == 0) break;
-        if (lo + c * step < hi) hi = lo + c * step;
-        lo = lo + (c - 1) * step + 1;
-    }
-    return lo;
 }
 
 template <bool RC>
@@ -70,29 +46,9 @@ __global__ __launch_bounds__(PW_TPB) void readscore_kernel(const uint32_t *__res
     for (int64_t t = (int64_t)blockIdx.x * PW_WAVES + wave; t < n_tiles; t += (int64_t)gridDim.x * PW_WAVES) {
         const int64_t g = t * PW_TILE_GROUPS + lane, tile0 = t * RS_TILE_POS;
         const Grp w = load_grp(codes, inval, g, n_data, lane);
-        // the reads of the tile: `base` start before it, those from base on are marked where they start
-        const int64_t base = reads_before(borders, n_seq, tile0, lane);
-        start_bits[wave][lane] = 0;
-        start_cnt[wave][lane] = 0;
-        wave_lds_sync();
-        for (int64_t r = base + lane;; r += KMAP_WAVE) {
-            const int64_t rel = r < n_seq ? borders[2 * r] - tile0 : (int64_t)RS_TILE_POS;
-            const bool in = rel >= 0 && rel < RS_TILE_POS;
-            if (in) {
-                atomicOr(&start_bits[wave][rel >> 4], 0x8000u >> (rel & 15));
-                atomicAdd(&start_cnt[wave][rel >> 4], 1u);
-            }
-            if (__ballot(in) != ~0ull) break;          // uniform: the starts ascend
-        }
-        wave_lds_sync();
-        const uint32_t sb = start_bits[wave][lane], sc = start_cnt[wave][lane];
-        uint32_t before = sc;                          // reads that start in the tile before this lane's group
-        for (int o = 1; o < KMAP_WAVE; o <<= 1) {
-            const uint32_t up = __shfl_up(before, o);
-            if (lane >= o) before += up;
-        }
-        before -= sc;
-        int64_t r = base + (int64_t)before - 1;        // the last read that starts before the group's first position; -1: none
+        // the reads of the tile (tile_read_starts, pwm_internal.h): r = the last read that starts before the group's first position
+        uint32_t sb, sc;
+        int64_t r = tile_read_starts(borders, n_seq, tile0, lane, start_bits[wave], start_cnt[wave], sb, sc);
         uint32_t loc0 = (uint32_t)(g * 16 - (r >= 0 ? borders[2 * r] : 0));    // loc of the group's first position (an int32 in a read)
         const bool shared_starts = sc != (uint32_t)__builtin_popcount(sb);
         uint64_t cur = 0, head = 0;                    // the running segment; the one that reached the lane from the left
@@ -108,8 +64,7 @@ __global__ __launch_bounds__(PW_TPB) void readscore_kernel(const uint32_t *__res
                     atomicMax(&key[r], (unsigned long long)cur);   // a read that began and ends in this group
                 }
                 cur = 0;
-                if (r + 1 < n_seq) ++r;
-                while (shared_starts && r + 1 < n_seq && borders[2 * (r + 1)] <= g * 16 + i) ++r;   // the last read that starts here
+                step_read(borders, n_seq, g * 16 + i, shared_starts, r);   // the last read that starts here
                 loc0 = (uint32_t)-i;
             }
             int fwd, rc;

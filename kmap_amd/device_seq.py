@@ -19,6 +19,10 @@ def _as_weights(W, who):
     return W
 
 
+LIBRARY_BATCH, LIBRARY_BATCH_CHUNKS = 8, 24    # csrc/pwm_library.hip: a batch is at most this many matrices and chunks of 4 columns
+LIBRARY_LDS_BINS, LIBRARY_MAX_BINS = 32768, 1 << 22      # ranges up to the first are counted in block-private bins; the second is the limit
+
+
 def _as_threshold(t, who):
     if not -2 ** 31 <= int(t) < 2 ** 31:
         raise ValueError(f"{who}: threshold {t} does not fit int32")
@@ -240,6 +244,34 @@ class DeviceSeq:
             raise
         out.n_scored = n_scored.value
         return out
+
+    def library_histograms(self, Ws, los, n_bins, revcom):
+        """For every weight matrix of Ws (int32 [4, width], widths may differ) the histogram of the reads' best scores over
+        [los[m], los[m] + n_bins[m]), as read_scores(W, revcom).histogram(lo, n_bins) gives it, from one pass over the original
+        reads per batch of matrices and without the per-read arrays (csrc/pwm_library.hip): returns
+        (list of uint64[n_bins[m]], n_outside int64[n_mat]: scorable reads whose best score lies outside the range -- they are in no
+        bin --, n_scored int64[n_mat]: reads with a valid window).  Needs no scan handle."""
+        Ws = [_as_weights(W, "library_histograms") for W in Ws]
+        los, n_bins = [int(x) for x in los], [int(x) for x in n_bins]
+        if not len(Ws) == len(los) == len(n_bins):
+            raise ValueError(f"library_histograms: {len(Ws)} matrices, {len(los)} range starts, {len(n_bins)} bin counts")
+        n_mat = len(Ws)
+        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
+        for m, (W, lo, nb) in enumerate(zip(Ws, los, n_bins)):
+            if not 4 <= W.shape[1] <= 31:
+                raise ValueError(f"library_histograms: matrix {m} has width {W.shape[1]}, outside 4..31")
+            if not 0 <= nb <= LIBRARY_MAX_BINS or not -2 ** 31 <= lo < 2 ** 31:
+                raise ValueError(f"library_histograms: matrix {m}: {nb} bins from {lo}, at most 2^22 bins of int32 scores are supported")
+            widths[m] = W.shape[1]
+            weights[m, :, :W.shape[1]] = W
+        lo_arr, nb_arr = np.array(los, np.int32).reshape(n_mat), np.array(n_bins, np.int64).reshape(n_mat)
+        flat = np.zeros(int(nb_arr.sum()), np.uint64)
+        outside, scored = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64)
+        check(_ffi.lib().kmap_readscore_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,
+                                                    ptr(widths), ptr(weights), ptr(lo_arr), ptr(nb_arr), int(bool(revcom)), ptr(flat),
+                                                    ptr(outside), ptr(scored), None))
+        ends = np.cumsum(nb_arr)
+        return [flat[e - nb:e] for e, nb in zip(ends.tolist(), nb_arr.tolist())], outside, scored
 
     def shuffled(self, klet=2, seed=0):
         """a new resident read set: every maximal run of valid bases of the ORIGINAL reads (inval_orig; a mask() before does not
