@@ -572,6 +572,13 @@ int kmap_embed_set_prob_lut(kmap_embed *e, const uint16_t *sums_rows_dev, int64_
  * repeated rows are stored once.  The map starts at 0, ends at src_rows - 1 and steps by 0 or 1 (checked).  NULL: one stored row per
  * session row again.  Results are those of the expanded matrix, bit for bit (same values through another address). */
 int kmap_embed_set_row_map(kmap_embed *e, const int32_t *rowmap_dev, int64_t src_rows);
+/* SEQ sessions, read-only: which force kernel forms the next kmap_embed_forces / kmap_embed_step launches, so that a test can assert the
+ * form it claims to pin.  out = {producer / adder form (1) or the row-owning forms (0) -- decided by the probability source, so ask
+ * after set_prob; rows [0, out[1]) of the session run in the pair / quad forms, of these [0, out[2]) in the pair form; lanes per row
+ * of the wide form that takes the rows from out[1] on (8, 16, 32, 64; 0: none); rows per block R and row slots RP (32 / 64) of the
+ * adder form (0: not considered for this shape); its producer waves M per SIMD without and EA on the SIMD with the adder (0 when
+ * out[0] is 0)}.  The split depends on the device's CU count and on KMAP_SEQ_FORM / KMAP_SEQ_TAIL / KMAP_SEQ_PAIR. */
+int kmap_embed_seq_geometry(const kmap_embed *e, int64_t out[8]);
 /* init: 2 x N coordinates, n_best placeholder snapshots (n_best x 2 x N), host arrays */
 int kmap_embed_set_coords(kmap_embed *e, const float *coords_2xn, const float *placeholders);
 /* jitter normals N(0, 0.01) pre-drawn (float64, as numpy draws them) from the host RNG stream,

@@ -160,6 +160,7 @@ _SIGS = {
     "kmap_embed_set_prob_f32": (i32, [vp, vp, i64]),
     "kmap_embed_set_prob_lut": (i32, [vp, vp, i64, vp, i32]),
     "kmap_embed_set_row_map": (i32, [vp, vp, i64]),
+    "kmap_embed_seq_geometry": (i32, [vp, P(i64)]),
     "kmap_embed_set_coords": (i32, [vp, vp, vp]),
     "kmap_embed_set_jitter": (i32, [vp, vp, i32]),
     "kmap_embed_forces": (i32, [vp, vp, vp, vp]),

@@ -1126,19 +1126,42 @@ void kmap_embed_seq_split(kmap_embed *e) {
     }
 }
 
+// producers of the adder form: M on each of the three SIMD classes without the adder, EA next to the adder.  One step each per chunk
+// where 3 M + EA can equal the producer steps per chunk (7 .. 13 of them), else as many as fit
+static void seq_adder_roles(const kmap_embed *e, int &M, int &EA) {
+    const int rps = e->seq_RP == 64 ? SaGeom<64, 128>::RPS : SaGeom<32, 256>::RPS;
+    const int steps = (e->seq_R + rps - 1) / rps;                     // producer steps per chunk
+    M = 4;
+    EA = 1;
+    if (steps <= 13) {
+        M = steps >= 12 ? 4 : steps >= 9 ? 3 : 2;
+        EA = steps - 3 * M;
+        if (EA < 0) EA = 0;
+        if (EA > 3) EA = 3;
+    }
+}
+int kmap_embed_seq_geometry(const kmap_embed *e, int64_t out[8]) {
+    KMAP_REQUIRE(e && out, "embed_seq_geometry: null");
+    KMAP_REQUIRE(e->mode == KMAP_EMBED_SEQ, "embed_seq_geometry: not a SEQ session");
+    const bool adder = seq_adder_form(e);
+    int M = 0, EA = 0;
+    if (adder) seq_adder_roles(e, M, EA);
+    const int64_t g[8] = {adder ? 1 : 0, e->seq_main_rows, e->seq_pair_rows, e->seq_tail_g, e->seq_R, e->seq_RP, M, EA};
+    for (int i = 0; i < 8; ++i) out[i] = g[i];
+    return KMAP_OK;
+}
+
 int kmap_embed_launch_seq(kmap_embed *e, float *G, hipStream_t st) {
     const bool lut = e->src.ps != nullptr;
     const size_t lds = lut ? (((size_t)e->src.lut_len * 4 + 15) & ~(size_t)15) : 16;
     if (seq_adder_form(e)) {
         const int nb = seq_adder_blocks(e);
+        int M, EA;
+        seq_adder_roles(e, M, EA);
 #define KMAP_SEQA(RP, CH)                                                                                                          \
     do {                                                                                                                           \
         const size_t lds_a = SaGeom<RP, CH>::FIXED_BYTES + lds;                                                                    \
         KMAP_TRY(kmap_allow_lds((const void *)forces_seqa_kernel<RP, CH>, (int)lds_a));                                            \
-        const int steps = (e->seq_R + SaGeom<RP, CH>::RPS - 1) / SaGeom<RP, CH>::RPS;     /* producer steps per chunk */                   \
-        /* producers: one step each per chunk where 3 M + EA can equal the steps (7 .. 13 of them), else as many as fit */          \
-        int M = 4, EA = 1;                                                                                                         \
-        if (steps <= 13) { M = steps >= 12 ? 4 : steps >= 9 ? 3 : 2; EA = steps - 3 * M; if (EA < 0) { EA = 0; } if (EA > 3) { EA = 3; } }          \
         const int waves = 4 * (M > EA + 1 ? M : EA + 1);                                                                           \
         const int geo = e->seq_R | (M << 8) | (EA << 12);                                                                          \
         forces_seqa_kernel<RP, CH><<<nb, KMAP_WAVE * waves, lds_a, st>>>(e->src, e->Y, e->n, e->row0, e->nrows, geo, G, e->loss_part); \

@@ -342,6 +342,13 @@ class EmbedSession:
             self._keep.append(rowmap)
             check(_ffi.lib().kmap_embed_set_row_map(self._h, rowmap.ptr, int(src_rows)))
 
+    def seq_geometry(self):
+        """SEQ sessions: the force kernel forms the next evaluation launches (kmap_embed_seq_geometry; ask after set_prob_*)."""
+        out = (_ffi.i64 * 8)()
+        check(_ffi.lib().kmap_embed_seq_geometry(self._h, out))
+        keys = ("adder", "main_rows", "pair_rows", "tail_g", "R", "RP", "M", "EA")
+        return dict(zip(keys, (int(v) for v in out)))
+
     def set_coords(self, coords, placeholders=None):
         coords = np.ascontiguousarray(coords, np.float32)
         ph = None if placeholders is None else np.ascontiguousarray(placeholders, np.float32)

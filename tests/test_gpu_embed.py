@@ -466,7 +466,10 @@ def test_seq_wide_tail_kernel_is_bit_identical(V, n, row0, nrows, tmp_path):
     LDS, same j-ascending f32 sum): the gradient must equal the all-quad kernel's (KMAP_SEQ_TAIL=0) bit for bit, whatever the
     split -- a full round + 1029 left-over rows (one-row waves), a row-sharded session, N = 5000 (all rows wide), a small N.
     The producer / adder form (KMAP_SEQ_FORM=adder; blocks of <= 32 or 64 rows, one adder wave each) must give the same bits too:
-    odd N (columns past n - 1 in the last chunk), a 31-row session, N below one chunk, a shard at the end of the rows."""
+    odd N (columns past n - 1 in the last chunk), a 31-row session, N below one chunk, a shard at the end of the rows.
+    None of these shapes selects the 8-lane wide form (a remainder of 4 x SIMDs + 1 .. 8 x SIMDs rows behind a full round) and the
+    yardstick here is another kernel: tests/test_gpu_seq_forms.py runs that form and holds every form, the quad one included, to the
+    host model of the reference arithmetic row by row."""
     import os
     import subprocess
     import sys
