@@ -300,6 +300,34 @@ int kmap_readscore_library_dev(const uint32_t *codes_dev, const uint16_t *inval_
                                uint64_t *hist_host, int64_t *n_outside /* host, n_mat */, int64_t *n_scored /* host, n_mat */,
                                void *stream);
 
+/* ---- count matrices against a library of count matrices (match_motifs; csrc/motif_match.hip) -- not in the
+ * reference.  A motif is a run of quantised columns: 4 x uint16 (A C G T, rint(1024 f), 0..1024) = 8 bytes per column, the columns of
+ * a set of motifs behind one another in one device array; the reverse complement of a motif is read from the same columns.  Column
+ * score s(x, y) = (1448 - floor(sqrt(sum_b (x_b - y_b)^2))) / 16, 0..90, in exact integers.  Widths, first columns, range lengths
+ * and table places are host arrays: they are checked (KMAP_E_INVAL: a width outside 4..31, columns or tables outside the arrays, a
+ * negative size, a NULL array) and packed into scratch memory, which costs one synchronisation of `stream` per call; the kernels
+ * are then asynchronous on it.
+ *   hist    hist_dev[c][s] (uint32, n_qcols x 91) = the library columns y, with revcom also their reversed-base twins, with
+ *           s(query column c, y) = s.  Integer adds only: exact in any order.
+ *   tables  for every query q (columns q_col0[q] .. + q_width[q] of hist_dev) and every range a..b of its columns with
+ *           L = b - a + 1 >= q_min_len[q]: sf[x] = sum_{y >= x} pmf[y], x = 0 .. 90 L, pmf = the convolution of hist rows a..b
+ *           divided by n_null; float64.  The tables of a query start at tables_dev + q_toff[q], by a, then by L, 90 L + 1 doubles
+ *           each.  Gathers in a fixed order, no floating atomics: the same bits in every run.
+ *   pairs   for every query q and target t: over the strands (+, with revcom also -) and offsets o, -(w_t - m) <= o <= w_q - m,
+ *           m = min(min_overlap, w_q, w_t), the configuration with the smallest sf_{a,b}[x] (x = the sum of the column scores of the
+ *           overlap a..b); exactly equal doubles: the larger L, then +, then the smaller o.  p_dev[q n_target + t] = that double,
+ *           cfg_dev[(q n_target + t) 4 ..] = o, strand (0 +, 1 -), L, x (int32).  q_min_len[q] must not exceed min_overlap or any
+ *           target width, and n_query is at most 65535. */
+int kmap_match_hist_dev(const uint16_t *qcols_dev, int64_t n_qcols, const uint16_t *lcols_dev, int64_t n_lcols, int revcom,
+                        uint32_t *hist_dev, void *stream);
+int kmap_match_tables_dev(const uint32_t *hist_dev, int64_t n_qcols, int64_t n_null, int n_query, const int32_t *q_width /* host */,
+                          const int64_t *q_col0 /* host */, const int32_t *q_min_len /* host */, const int64_t *q_toff /* host */,
+                          double *tables_dev, int64_t n_table /* doubles */, void *stream);
+int kmap_match_pairs_dev(const uint16_t *qcols_dev, int64_t n_qcols, int n_query, const int32_t *q_width, const int64_t *q_col0,
+                         const int32_t *q_min_len, const int64_t *q_toff, const double *tables_dev, int64_t n_table,
+                         const uint16_t *lcols_dev, int64_t n_lcols, int n_target, const int32_t *t_width /* host */,
+                         const int64_t *t_col0 /* host */, int min_overlap, int revcom, double *p_dev, int32_t *cfg_dev, void *stream);
+
 /* ---- k-mer enrichment against a control table (enrich_kmers; csrc/enrich.hip) -- not in the reference.
  * Foreground F: any counts handle (its order is kept; it need not ascend).  Control B: a counts handle counted WITHOUT the
  * reverse-complement merge, keys ascending and unique.  Per foreground entry (x, a): b = B[x] + (revcom ? B[rc x] : 0), a missing key

@@ -3,7 +3,7 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and seven verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+figures), and eight verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
 its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
 write, with a strand, a score and a p-value threshold per hit (pwm.py), and `enrich_kmers`, the k-mers and motifs of a result
 directory scored against control reads instead of the uniform null: both read sets counted on the GPU, the tables joined there, a
@@ -13,7 +13,9 @@ window score of every read and of every control read under a count matrix, compa
 by the two-proportion z at every score threshold (evaluate.py), and `shuffle_reads`, the control reads for those two when there is
 no second read set: every read shuffled on the GPU so that its length, its N and its base or dinucleotide counts stay (shuffle.py), and
 `rank_motif_library`, evaluate_pwm's comparison for a whole library of known motifs (MEME text or count matrices) in batched passes
-over the reads, ranked, with Benjamini-Hochberg q-values (library.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+over the reads, ranked, with Benjamini-Hochberg q-values (library.py), and `match_motifs`, count matrices compared with a library of
+count matrices column by column, at every offset and on both strands, with a p-value from the library's own columns: the nearest
+known motif of a discovered one, and the families of a library matched against itself (motif_match.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -218,6 +220,30 @@ def rank_motif_library(res_dir, control_fasta_file, library_file, p_value=1e-4, 
     from .library import _rank_motif_library
     _rank_motif_library(res_dir, control_fasta_file, list(library_file), p_value, pseudocount, nsites_default, revcom_mode, min_reads,
                         top_hist, output_dir)
+
+
+@cli.command(name="match_motifs")
+@click.option("--query_file", type=str, required=True, multiple=True,
+              help="query motifs: a 4 x w base-count matrix CSV, a MEME minimal text file, or a directory of *.meme and *.csv files; "
+                   "may be given several times")
+@click.option("--library_file", type=str, required=False, multiple=True,
+              help="motif library, in the same formats; may be given several times (default: the queries are matched against "
+                   "themselves and grouped into families)")
+@click.option("--revcom_mode", type=bool, default=True, required=False, help="also try the reverse complement of every target")
+@click.option("--min_overlap", type=int, default=5, required=False,
+              help="fewest columns two motifs overlap in (at least 1; a motif narrower than this overlaps in all its columns)")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base)")
+@click.option("--nsites_default", type=int, default=20, required=False,
+              help="sites behind a MEME motif without nsites= (its probabilities become counts of this many sites)")
+@click.option("--top_n", type=int, default=10, required=False, help="targets listed per query")
+@click.option("--family_e_value", type=float, default=0.01, required=False,
+              help="all against all: two motifs are linked when each finds the other with an E-value of at most this")
+@click.option("--output_dir", type=str, default="./motif_matches", required=False, help="Output directory")
+def match_motifs(query_file, library_file=(), revcom_mode=True, min_overlap=5, pseudocount=1.0, nsites_default=20, top_n=10,
+                 family_e_value=0.01, output_dir="./motif_matches"):
+    from .motif_match import _match_motifs
+    _match_motifs(list(query_file), list(library_file), revcom_mode, min_overlap, pseudocount, nsites_default, top_n, family_e_value,
+                  output_dir)
 
 
 @cli.command(name="shuffle_reads")
