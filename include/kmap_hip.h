@@ -300,6 +300,24 @@ int kmap_readscore_library_dev(const uint32_t *codes_dev, const uint16_t *inval_
                                uint64_t *hist_host, int64_t *n_outside /* host, n_mat */, int64_t *n_scored /* host, n_mat */,
                                void *stream);
 
+/* ---- where in the reads the best site of every matrix of a library lies (motif_centrality; csrc/pwm_sites.hip, DESIGN.md section
+ * 18) -- not in the reference.  Matrices, batches and argument rules are kmap_readscore_library_dev's.  A site read of matrix m is a
+ * read whose best window (kmap_readscore_packed_dev's: the largest score, on a tie the smallest loc) scores thresholds[m] or more;
+ * L = its length (borders[r][1] - borders[r][0]), d = 2 loc + widths[m] - L its doubled centre offset, -(L - width) <= d <= L - width.
+ * Per matrix, over its site reads with L <= max_len: pos_hist_host[m (2 max_len + 1) + d + max_len] = site reads with offset d,
+ * len_hist_host[m (max_len + 1) + L] = site reads of length L, n_sites[m] = their number (the sum of either histogram);
+ * n_too_long[m] = site reads with L > max_len, which are in neither histogram.  Blocking (one synchronisation per batch); integer
+ * maxima and counts only, so two calls give the same numbers; scratch memory only, no handle.  KMAP_E_INVAL: a width outside 4..31,
+ * a weight of 2^31 / 31 or more in magnitude or behind the width, a negative size or max_len, a NULL array; KMAP_E_UNSUP: max_len
+ * above 2^20.  n_mat == 0 writes nothing; n_seq == 0 or n == 0 gives zeros. */
+int kmap_readscore_sites_library_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
+                                     const int64_t *borders_dev, int64_t n_seq,
+                                     int n_mat, const int32_t *widths /* host */, const int32_t *weights /* host, n_mat x [4][32] */,
+                                     const int32_t *thresholds /* host, n_mat */, int revcom, int64_t max_len,
+                                     uint64_t *pos_hist_host /* n_mat x (2 max_len + 1) */,
+                                     uint64_t *len_hist_host /* n_mat x (max_len + 1) */,
+                                     int64_t *n_sites /* host, n_mat */, int64_t *n_too_long /* host, n_mat */, void *stream);
+
 /* ---- count matrices against a library of count matrices (match_motifs; csrc/motif_match.hip) -- not in the
  * reference.  A motif is a run of quantised columns: 4 x uint16 (A C G T, rint(1024 f), 0..1024) = 8 bytes per column, the columns of
  * a set of motifs behind one another in one device array; the reverse complement of a motif is read from the same columns.  Column

@@ -3,7 +3,7 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and eight verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+figures), and nine verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
 its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
 write, with a strand, a score and a p-value threshold per hit (pwm.py), and `enrich_kmers`, the k-mers and motifs of a result
 directory scored against control reads instead of the uniform null: both read sets counted on the GPU, the tables joined there, a
@@ -15,7 +15,9 @@ no second read set: every read shuffled on the GPU so that its length, its N and
 `rank_motif_library`, evaluate_pwm's comparison for a whole library of known motifs (MEME text or count matrices) in batched passes
 over the reads, ranked, with Benjamini-Hochberg q-values (library.py), and `match_motifs`, count matrices compared with a library of
 count matrices column by column, at every offset and on both strands, with a p-value from the library's own columns: the nearest
-known motif of a discovered one, and the families of a library matched against itself (motif_match.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+known motif of a discovered one, and the families of a library matched against itself (motif_match.py), and `motif_centrality`,
+where in the reads the best site of every motif of a library lies: the sites within a half-width of the read centre against a site
+placed uniformly, the half-width with the largest z, ranked, with q-values, no control needed (centrality.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -244,6 +246,34 @@ def match_motifs(query_file, library_file=(), revcom_mode=True, min_overlap=5, p
     from .motif_match import _match_motifs
     _match_motifs(list(query_file), list(library_file), revcom_mode, min_overlap, pseudocount, nsites_default, top_n, family_e_value,
                   output_dir)
+
+
+@cli.command(name="motif_centrality")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--library_file", type=str, required=True, multiple=True,
+              help="motif library: a MEME minimal text file, a 4 x w base-count matrix CSV (as for evaluate_pwm), or a directory of "
+                   "*.meme and *.csv files; may be given several times")
+@click.option("--control_fasta_file", type=str, default=None, required=False,
+              help="FASTA file of control reads: the share of sites inside the best region is compared with theirs (optional)")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="a read is a site read when its best window reaches scan_pwm's threshold of this p-value (per strand and per position)")
+@click.option("--min_score", type=float, default=None, required=False,
+              help="score threshold in bits; replaces the threshold derived from --p_value")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base)")
+@click.option("--nsites_default", type=int, default=20, required=False,
+              help="sites behind a MEME motif without nsites= (its probabilities become counts of this many sites)")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="score both strands and keep the better one (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--min_half", type=int, default=0, required=False,
+              help="smallest half-width tried, in half bases (the doubled distance of a site's centre from the read's centre)")
+@click.option("--min_sites", type=int, default=10, required=False, help="a motif with fewer site reads gets no z (p = 1)")
+@click.option("--top_hist", type=int, default=5, required=False, help="also write the site offsets of this many best-ranked motifs")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: motif_centrality in res_dir)")
+def motif_centrality(res_dir, library_file, control_fasta_file=None, p_value=1e-4, min_score=None, pseudocount=1.0, nsites_default=20,
+                     revcom_mode=None, min_half=0, min_sites=10, top_hist=5, output_dir=None):
+    from .centrality import _motif_centrality
+    _motif_centrality(res_dir, list(library_file), control_fasta_file, p_value, min_score, pseudocount, nsites_default, revcom_mode,
+                      min_half, min_sites, top_hist, output_dir)
 
 
 @cli.command(name="shuffle_reads")

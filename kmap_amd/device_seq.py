@@ -21,6 +21,7 @@ def _as_weights(W, who):
 
 LIBRARY_BATCH, LIBRARY_BATCH_CHUNKS = 8, 24    # csrc/pwm_library.hip: a batch is at most this many matrices and chunks of 4 columns
 LIBRARY_LDS_BINS, LIBRARY_MAX_BINS = 32768, 1 << 22      # ranges up to the first are counted in block-private bins; the second is the limit
+SITES_MAX_LEN = 1 << 20                        # csrc/pwm_sites.hip: the longest read library_sites makes histograms for
 
 
 def _as_threshold(t, who):
@@ -272,6 +273,46 @@ class DeviceSeq:
                                                     ptr(outside), ptr(scored), None))
         ends = np.cumsum(nb_arr)
         return [flat[e - nb:e] for e, nb in zip(ends.tolist(), nb_arr.tolist())], outside, scored
+
+    def max_read_len(self):
+        """the largest read length: from the host's lengths, or for reads that only exist in HBM from the borders, fetched once"""
+        if self.read_len is None:
+            b = self.borders.to_numpy(np.int64, (self.n_seq, 2))
+            _ffi.sync()
+            self.read_len = (b[:, 1] - b[:, 0]).astype(np.int64)
+        return int(self.read_len.max()) if self.n_seq else 0
+
+    def library_sites(self, Ws, thresholds, revcom, max_len=None):
+        """For every weight matrix of Ws (int32 [4, width], widths may differ) where the best window of its site reads lies
+        (csrc/pwm_sites.hip).  A site read is a read whose best window (read_scores': the largest score, the
+        smallest loc on a tie) scores thresholds[m] or more; with L its length, d = 2 loc + width - L is the window's doubled
+        centre offset.  Returns (D int64[n_mat][2 max_len + 1]: D[m][d + max_len] = site reads with offset d, Hlen
+        int64[n_mat][max_len + 1]: site reads of length L, n_sites int64[n_mat]: the sum of either, n_too_long int64[n_mat]: site
+        reads longer than max_len, which are in neither histogram).  max_len None: the largest read length.  One pass over the
+        original reads per batch of matrices, nothing per read leaves the device.  Needs no scan handle."""
+        Ws = [_as_weights(W, "library_sites") for W in Ws]
+        thresholds = [_as_threshold(t, "library_sites") for t in thresholds]
+        if len(Ws) != len(thresholds):
+            raise ValueError(f"library_sites: {len(Ws)} matrices, {len(thresholds)} thresholds")
+        n_mat = len(Ws)
+        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
+        for m, W in enumerate(Ws):
+            if not 4 <= W.shape[1] <= 31:
+                raise ValueError(f"library_sites: matrix {m} has width {W.shape[1]}, outside 4..31")
+            widths[m] = W.shape[1]
+            weights[m, :, :W.shape[1]] = W
+        if max_len is not None and (isinstance(max_len, bool) or int(max_len) != max_len or not 0 <= max_len <= SITES_MAX_LEN):
+            raise ValueError(f"library_sites: max_len {max_len} outside 0 .. 2^20")
+        max_len = self.max_read_len() if max_len is None else int(max_len)
+        if max_len > SITES_MAX_LEN:
+            raise ValueError(f"library_sites: the longest read has {max_len} bases, more than 2^20")
+        thr = np.array(thresholds, np.int32).reshape(n_mat)
+        D, Hlen = np.zeros((n_mat, 2 * max_len + 1), np.uint64), np.zeros((n_mat, max_len + 1), np.uint64)
+        sites, too_long = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64)
+        check(_ffi.lib().kmap_readscore_sites_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,
+                                                          ptr(widths), ptr(weights), ptr(thr), int(bool(revcom)), max_len, ptr(D),
+                                                          ptr(Hlen), ptr(sites), ptr(too_long), None))
+        return D.astype(np.int64), Hlen.astype(np.int64), sites, too_long
 
     def shuffled(self, klet=2, seed=0):
         """a new resident read set: every maximal run of valid bases of the ORIGINAL reads (inval_orig; a mask() before does not
