@@ -29,9 +29,13 @@ constexpr int WAVES_PER_BLOCK = 8;   // max; launch uses wpb <= this
 // pairs with equal non-zero gid are compared on the first clen bases, i.e. (a^b) >> gshift[g].
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-struct ByteTab {   // passed by value in the kernarg segment (no H2D copy, no sync)
+union ByteTab {   // passed by value in the kernarg segment (no H2D copy, no sync)
     uint8_t v[256];
+    uint32_t w[64];   // the same bytes as aligned words, for at()
 };
+// t.v[i] for a wave-uniform i: the aligned word goes through the scalar unit.  A byte load is a vector load even at a uniform
+// address, and inside the tile kernel's row loop its s_waitcnt vmcnt(0) also waited for every store the wave had issued.
+__device__ __forceinline__ uint32_t at(const ByteTab &t, uint32_t i) { return (t.w[i >> 2] >> (8 * (i & 3))) & 0xFFu; }
 
 __global__ void build_gid_kernel(const int32_t *__restrict__ label, int64_t n, ByteTab lab2gid, int n_lab,
                                  uint8_t *__restrict__ gid) {
@@ -180,11 +184,14 @@ __global__ __launch_bounds__(KMAP_WAVE *WAVES_PER_BLOCK) void hamdist_matrix_ker
 // a normal tile there keeps one or two waves busy and lets the others leave at once, yet holds one of the CU's four slots for
 // a whole residency (N = 50 000: 848 of 4096 columns, 1/13 of all tiles for 1.7 % of the bytes).  That block is tiled on its
 // own: a tail workgroup covers m = 4 / tw row sets of its chunk column, wave w taking row set w / tw and column quarter
-// w % tw, so all four waves store and there are m times fewer tail workgroups.  A row set is R rows spaced 8 apart with the
-// workgroup's residue, exactly a normal tile's rows, so (a) and (b) hold as they are and (c) is the same LDS reservation.
+// w % tw, so all four waves store and there are m times fewer tail workgroups.  A tail row set is RT rows spaced 8 apart with
+// the workgroup's residue, a normal tile's rows when RT = R, so (a) and (b) hold as they are and (c) is the same LDS
+// reservation.  The tail's rows are tiled on their own, so RT need not be R: RT = 8 for every instantiation (measured at
+// N = 50 000, k = 8, where R = 4: the benchmark's step is 2 % shorter with RT = 8 than with 4, RT = 2 equals 4 and 16 lies
+// between; CHANGELOG.md).
 // The grid is one-dimensional, so no workgroup is launched for a (column block, row group) nobody owns: first the
-// 8 * cbm * groups normal tiles in row-group order (column blocks fastest), then the 8 * ceil(groups / m) tail tiles; both
-// counts are multiples of 8, so (id & 7) is a block's XCD.
+// 8 * cbm * groups normal tiles in row-group order (column blocks fastest), then the 8 * ceil(tail groups / m) tail tiles;
+// both counts are multiples of 8, so (id & 7) is a block's XCD.
 constexpr int T_TPB = 256;
 constexpr int T_WAVES = T_TPB / KMAP_WAVE;
 constexpr int T_LDS_THROTTLE = 40 * 1024;   // dynamic LDS reserved per block: four resident blocks per CU (rule (c) above)
@@ -211,7 +218,7 @@ __global__ void build_codes_kernel(const H *__restrict__ kh, int64_t n, int k, H
 
 __device__ __forceinline__ uint32_t bcnt(uint32_t x, uint32_t acc) { return (uint32_t)__builtin_popcount(x) + acc; }
 
-template <int CW, int R>
+template <int CW, int R, int RT>
 __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__restrict__ c0, const uint32_t *__restrict__ c1,
                                                              const uint8_t *__restrict__ gid, ByteTab gshift, int k, int64_t n,
                                                              int64_t row0, int64_t nrows, uint8_t *__restrict__ out, int64_t ld,
@@ -223,7 +230,7 @@ __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__r
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const bool tail = id >= n_main;                                   // block-uniform
     int c, q;                     // column block, 1024-column quarter of it
-    int64_t g;                    // row set: rows g * 8 R + rho + 8 j
+    int64_t g;                    // row set: rows g * 8 rcnt + rho + 8 j
     if (!tail) {
         // y = id / w8 without a division: cbm_magic = floor(2^32 / w8) gives the quotient or one less
         const uint32_t w8 = 8u * (uint32_t)cbm;
@@ -238,13 +245,16 @@ __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__r
         q = wave & (tw - 1);
     }
     const int rho = ((((x - c - shift) % 8 + 8) % 8) * inv) & 7;      // (ld/4096 * row + c + shift) % 8 == x
-    const int64_t rbase = g * (8 * R) + rho;
+    constexpr int RM = RT > R ? RT : R;
+    const int rcnt = tail ? RT : R;                                   // rows of this block's row sets
+    const int64_t rbase = g * (8 * rcnt) + rho;
     // the wave's row codes / group ids: one vector load per wave up front (lane j holds row j), v_readlane per row.
-    // Nothing is loaded inside the row loop, so no s_waitcnt vmcnt ever waits on the stores already issued.  Loaded BEFORE
-    // lanes past the last column leave: v_readlane must find lanes 0..R-1 written even in a wave that keeps only lane 0.
+    // Nothing is loaded through the vector unit inside the row loop (the shift table: at()), so no s_waitcnt vmcnt ever
+    // waits on the stores already issued.  Loaded BEFORE lanes past the last column leave: v_readlane must find lanes
+    // 0..rcnt-1 written even in a wave that keeps only lane 0.
     const int lane = threadIdx.x & (KMAP_WAVE - 1);
-    const int64_t my_rl = rbase + 8 * (lane < R ? lane : 0);
-    const bool rv = lane < R && my_rl < nrows;
+    const int64_t my_rl = rbase + 8 * (lane < RM ? lane : 0);
+    const bool rv = lane < rcnt && my_rl < nrows;
     const uint32_t ra0 = rv ? c0[row0 + my_rl] : 0u;
     const uint32_t ra1 = (CW == 2 && rv) ? c1[row0 + my_rl] : 0u;
     const uint32_t rgid = rv ? (uint32_t)gid[row0 + my_rl] : 0u;
@@ -294,9 +304,9 @@ __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__r
     const bool lane_uniform = full && gcol[0] == lane_g * 0x01010101u && gcol[1] == gcol[0] && gcol[2] == gcol[0] && gcol[3] == gcol[0];
 
 #pragma unroll
-    for (int j = 0; j < R; ++j) {
+    for (int j = 0; j < RM; ++j) {
         const int64_t rloc = rbase + 8 * j;                      // row inside this call's output (wave-uniform)
-        if (rloc >= nrows) break;
+        if (rloc >= nrows || j >= rcnt) break;
         const uint32_t a0 = rl(ra0, j);
         const uint32_t a1 = (CW == 2) ? rl(ra1, j) : 0u;
         const uint32_t rg = rl(rgid, j);
@@ -312,7 +322,7 @@ __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__r
                     w[v] = acc;
                 }
             } else {
-                const uint32_t sh = (uint32_t)gshift.v[rg];
+                const uint32_t sh = at(gshift, rg);
                 const bool w_same = __all(lane_uniform && lane_g == rg), w_none = __all(lane_uniform && lane_g != rg);
                 if (w_same || w_none) {   // whole wave inside / outside the row's group (see the one-hot branch below)
                     const uint32_t s2 = w_same ? sh : 0u;
@@ -351,7 +361,7 @@ __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__r
                 w[v] = acc;
             }
         } else {   // row of a short consensus: same-group pairs are compared on the first clen bases (= low 4*clen code bits)
-            const int clen = k - (int)(gshift.v[rg] >> 1);
+            const int clen = k - (int)(at(gshift, rg) >> 1);
             const uint64_t pm = (clen >= 16) ? ~0ull : ((1ull << (4 * clen)) - 1ull);
             const uint32_t p0 = a0 & (uint32_t)pm, p1 = a1 & (uint32_t)(pm >> 32);
             // labels arrive grouped (sample_disp_kmer emits label after label), so nearly every wave's 1024 columns lie entirely
@@ -398,7 +408,7 @@ __global__ __launch_bounds__(T_TPB) void hamdist_tile_kernel(const uint32_t *__r
     }
 }
 
-template <int CW, int R>
+template <int CW, int R, int RT>
 int launch_tile(const uint32_t *c0, const uint32_t *c1, const uint8_t *gid, const ByteTab &gshift, int k, int64_t n, int64_t row0,
                 int64_t nrows, uint8_t *out, int64_t ld, hipStream_t st) {
     const int cb = (int)((n + 4095) / 4096);
@@ -414,11 +424,12 @@ int launch_tile(const uint32_t *c0, const uint32_t *c1, const uint8_t *gid, cons
     const int cbm = pack ? cb - 1 : cb;                      // column blocks served by normal tiles
     const int64_t groups = (nrows + 8 * R - 1) / (8 * R);
     const int m = pack ? T_WAVES / tw : 1;                   // row sets per tail workgroup
-    const int64_t n_main = 8 * cbm * groups, n_tail = pack ? 8 * ((groups + m - 1) / m) : 0;
+    const int64_t tgroups = (nrows + 8 * RT - 1) / (8 * RT);   // row groups of the tail's RT-row sets
+    const int64_t n_main = 8 * cbm * groups, n_tail = pack ? 8 * ((tgroups + m - 1) / m) : 0;
     KMAP_REQUIRE(n_main + n_tail <= (int64_t)T_MAX_BLOCKS, "hamdist_matrix: %lld rows x %lld columns are too many tiles for one launch",
                  (long long)nrows, (long long)n);
-    KMAP_TRY(kmap_allow_lds((const void *)hamdist_tile_kernel<CW, R>, 160 * 1024));
-    hamdist_tile_kernel<CW, R><<<dim3((unsigned)(n_main + n_tail)), T_TPB, T_LDS_THROTTLE, st>>>(
+    KMAP_TRY(kmap_allow_lds((const void *)hamdist_tile_kernel<CW, R, RT>, 160 * 1024));
+    hamdist_tile_kernel<CW, R, RT><<<dim3((unsigned)(n_main + n_tail)), T_TPB, T_LDS_THROTTLE, st>>>(
         c0, c1, gid, gshift, k, n, row0, nrows, out, ld, cbm, (uint32_t)((1ull << 32) / (8u * (unsigned)cbm)), (uint32_t)n_main, pack ? tw : 0,
         inv, shift);
     KMAP_CHECK_HIP(hipGetLastError());
@@ -464,9 +475,9 @@ int launch_matrix(const H *kh_dev, const int32_t *label_dev, int64_t n, int k, c
         uint32_t *c0 = codes, *c1 = (onehot == 2) ? codes + npad : nullptr;
         build_codes_kernel<H><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(kh_dev, n, k, low_mask<H>(k), onehot, c0, c1,
                                                                                        label_dev, lab2gid, n_lab, gid);
-        if (onehot == 1) return launch_tile<1, 4>(c0, c1, gid, gshift, k, n, row0, nrows, out_dev, ld, st);
-        if (onehot == 0) return launch_tile<0, 8>(c0, c1, gid, gshift, k, n, row0, nrows, out_dev, ld, st);
-        return launch_tile<2, 8>(c0, c1, gid, gshift, k, n, row0, nrows, out_dev, ld, st);
+        if (onehot == 1) return launch_tile<1, 4, 8>(c0, c1, gid, gshift, k, n, row0, nrows, out_dev, ld, st);
+        if (onehot == 0) return launch_tile<0, 8, 8>(c0, c1, gid, gshift, k, n, row0, nrows, out_dev, ld, st);
+        return launch_tile<2, 8, 8>(c0, c1, gid, gshift, k, n, row0, nrows, out_dev, ld, st);
     }
     // general kernel: k > 16, small or unaligned outputs
     build_gid_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(label_dev, n, lab2gid, n_lab, gid);
