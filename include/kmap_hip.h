@@ -318,6 +318,35 @@ int kmap_readscore_sites_library_dev(const uint32_t *codes_dev, const uint16_t *
                                      uint64_t *len_hist_host /* n_mat x (max_len + 1) */,
                                      int64_t *n_sites /* host, n_mat */, int64_t *n_too_long /* host, n_mat */, void *stream);
 
+/* ---- at which distance and in which orientation the best site of every matrix of a library lies from a primary matrix's site
+ * (motif_spacing; csrc/pwm_spacing.hip) -- not in the reference.  Matrices, batches and argument rules are
+ * kmap_readscore_library_dev's.  prim_score_dev / prim_loc_dev / prim_strand_dev are kmap_readscore_packed_dev's three arrays for
+ * the primary matrix of prim_width columns: read r is a primary read when prim_loc_dev[r] >= 0 and prim_score_dev[r] >=
+ * prim_threshold; p = its loc, sP its strand, *n_primary their number.  The secondary site of matrix m in a primary read of
+ * length L is the best window (largest score, then smallest loc; a strand tie is '+') among the valid windows that score
+ * thresholds[m] or more and do not overlap the primary window: loc + w <= p (left, gap g = p - loc - w) or loc >= p + prim_width
+ * (right, g = loc - p - prim_width).  n_pair[m] = primary reads with one; those with g > max_gap are in n_far[m] and in no
+ * histogram, and so is a read whose borders do not hold both windows.  The others count once in each histogram:
+ *   gap_hist_host[(m 4 + q)(max_gap + 1) + g], q = 2 downstream + opposite, downstream = (right) != (sP is '-'), opposite = the
+ *     secondary's strand differs from sP;
+ *   room_hist_host[(m (max_gap + 2) + u)(max_gap + 2) + d], (u, d) = the upstream and downstream rooms: left room =
+ *     min(max(p - w + 1, 0), max_gap + 1), right room = min(max(L - p - prim_width - w + 1, 0), max_gap + 1), the left one is u
+ *     when sP is '+'.
+ * Blocking (one synchronisation per batch); integer maxima and counts only, so two calls give the same numbers; scratch memory
+ * only, no handle.  KMAP_E_INVAL: a width or prim_width outside 4..31, a weight of 2^31 / 31 or more in magnitude or behind the
+ * width, a negative size or max_gap, a NULL array; KMAP_E_UNSUP: max_gap above 511.  n_mat == 0 gives *n_primary alone; n_seq == 0
+ * or n == 0 gives zeros (and *n_primary). */
+int kmap_readscore_spacing_library_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
+                                       const int64_t *borders_dev, int64_t n_seq,
+                                       const int32_t *prim_score_dev, const int32_t *prim_loc_dev, const uint8_t *prim_strand_dev,
+                                       int prim_width, int32_t prim_threshold,
+                                       int n_mat, const int32_t *widths /* host */, const int32_t *weights /* host, n_mat x [4][32] */,
+                                       const int32_t *thresholds /* host, n_mat */, int revcom, int max_gap,
+                                       uint64_t *gap_hist_host /* n_mat x 4 x (max_gap + 1) */,
+                                       uint64_t *room_hist_host /* n_mat x (max_gap + 2) x (max_gap + 2) */,
+                                       int64_t *n_primary /* host, one */, int64_t *n_pair /* host, n_mat */,
+                                       int64_t *n_far /* host, n_mat */, void *stream);
+
 /* ---- count matrices against a library of count matrices (match_motifs; csrc/motif_match.hip) -- not in the
  * reference.  A motif is a run of quantised columns: 4 x uint16 (A C G T, rint(1024 f), 0..1024) = 8 bytes per column, the columns of
  * a set of motifs behind one another in one device array; the reverse complement of a motif is read from the same columns.  Column

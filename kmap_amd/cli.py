@@ -3,7 +3,7 @@
 with the same option names, plus `ex_hamball` (motif_discovery.py:74-108; Hamming-ball extraction on the GPU),
 `extract_motif_locations` (util.py:42-71; motif hits mapped to genome coordinates through a BED file, merged and sorted on the GPU)
 and `check_motif_co_occurence` (motif_discovery.py:111-177; occurrence scan of two user motifs and their co-occurrence tables, no
-figures), and nine verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
+figures), and ten verbs the reference does not have: `project_kmers`, new k-mers placed on the map `visualize_kmers` wrote, without moving
 its points (projection.py), and `scan_pwm`, every read position scored against the base-count matrices scan_motif and ex_hamball
 write, with a strand, a score and a p-value threshold per hit (pwm.py), and `enrich_kmers`, the k-mers and motifs of a result
 directory scored against control reads instead of the uniform null: both read sets counted on the GPU, the tables joined there, a
@@ -17,7 +17,10 @@ over the reads, ranked, with Benjamini-Hochberg q-values (library.py), and `matc
 count matrices column by column, at every offset and on both strands, with a p-value from the library's own columns: the nearest
 known motif of a discovered one, and the families of a library matched against itself (motif_match.py), and `motif_centrality`,
 where in the reads the best site of every motif of a library lies: the sites within a half-width of the read centre against a site
-placed uniformly, the half-width with the largest z, ranked, with q-values, no control needed (centrality.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+placed uniformly, the half-width with the largest z, ranked, with q-values, no control needed (centrality.py), and `motif_spacing`,
+at which distance, on which side and on which relative strand of a primary motif's site the best non-overlapping site of every motif
+of a library lies: pair reads per (side, strand, gap) bin against a uniformly placed site, a Poisson tail for the best bin, ranked,
+with q-values (spacing.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -274,6 +277,39 @@ def motif_centrality(res_dir, library_file, control_fasta_file=None, p_value=1e-
     from .centrality import _motif_centrality
     _motif_centrality(res_dir, list(library_file), control_fasta_file, p_value, min_score, pseudocount, nsites_default, revcom_mode,
                       min_half, min_sites, top_hist, output_dir)
+
+
+@cli.command(name="motif_spacing")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--primary_file", type=str, required=True,
+              help="the primary motif: a 4 x w base-count matrix CSV or a MEME minimal text file with exactly one motif that can be "
+                   "scored (or --primary_name)")
+@click.option("--primary_name", type=str, default=None, required=False, help="the motif of --primary_file to take, by its name")
+@click.option("--library_file", type=str, required=True, multiple=True,
+              help="motif library: a MEME minimal text file, a 4 x w base-count matrix CSV (as for evaluate_pwm), or a directory of "
+                   "*.meme and *.csv files; may be given several times")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="a window is a site when it reaches scan_pwm's threshold of this p-value (per strand and per position); for the "
+                   "primary motif and the library")
+@click.option("--primary_min_score", type=float, default=None, required=False,
+              help="score threshold of the primary motif in bits; replaces the threshold derived from --p_value")
+@click.option("--min_score", type=float, default=None, required=False,
+              help="score threshold of the library motifs in bits; replaces the thresholds derived from --p_value")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base)")
+@click.option("--nsites_default", type=int, default=20, required=False,
+              help="sites behind a MEME motif without nsites= (its probabilities become counts of this many sites)")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="score both strands and keep the better one (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--max_gap", type=int, default=150, required=False,
+              help="largest number of bases between the two sites that gets a bin (0..511); pairs further apart are counted as far")
+@click.option("--min_pairs", type=int, default=10, required=False, help="a motif with fewer pair reads within --max_gap gets no bin (p = 1)")
+@click.option("--top_hist", type=int, default=5, required=False, help="also write the gap histograms of this many best-ranked motifs")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: motif_spacing in res_dir)")
+def motif_spacing(res_dir, primary_file, library_file, primary_name=None, p_value=1e-4, primary_min_score=None, min_score=None,
+                  pseudocount=1.0, nsites_default=20, revcom_mode=None, max_gap=150, min_pairs=10, top_hist=5, output_dir=None):
+    from .spacing import _motif_spacing
+    _motif_spacing(res_dir, primary_file, list(library_file), primary_name, p_value, primary_min_score, min_score, pseudocount,
+                   nsites_default, revcom_mode, max_gap, min_pairs, top_hist, output_dir)
 
 
 @cli.command(name="shuffle_reads")

@@ -22,6 +22,7 @@ def _as_weights(W, who):
 LIBRARY_BATCH, LIBRARY_BATCH_CHUNKS = 8, 24    # csrc/pwm_library.hip: a batch is at most this many matrices and chunks of 4 columns
 LIBRARY_LDS_BINS, LIBRARY_MAX_BINS = 32768, 1 << 22      # ranges up to the first are counted in block-private bins; the second is the limit
 SITES_MAX_LEN = 1 << 20                        # csrc/pwm_sites.hip: the longest read library_sites makes histograms for
+SPACING_MAX_GAP = 511                          # csrc/pwm_spacing.hip: the largest gap library_spacing makes histograms for
 
 
 def _as_threshold(t, who):
@@ -313,6 +314,45 @@ class DeviceSeq:
                                                           ptr(widths), ptr(weights), ptr(thr), int(bool(revcom)), max_len, ptr(D),
                                                           ptr(Hlen), ptr(sites), ptr(too_long), None))
         return D.astype(np.int64), Hlen.astype(np.int64), sites, too_long
+
+    def library_spacing(self, primary, prim_width, prim_threshold, Ws, thresholds, revcom, max_gap=150):
+        """For every weight matrix of Ws (int32 [4, width], widths may differ) at which distance and in which orientation its best
+        site lies from the primary matrix's site (csrc/pwm_spacing.hip).  `primary` is the ReadScores of the
+        primary matrix (read_scores(W_P, revcom), still in HBM) of prim_width columns: a read whose best window scores
+        prim_threshold or more is a primary read, p that window's loc and sP its strand.  The secondary site of matrix m is the
+        best window (read_scores' order) among the valid windows that score thresholds[m] or more and do not overlap the primary
+        window; its gap g counts the bases between the two windows.  Returns (S int64[n_mat, 4, max_gap + 1]: S[m][2 downstream
+        + opposite][g] = pair reads, the side told in the primary's orientation, R int64[n_mat, max_gap + 2, max_gap + 2]:
+        R[m][u][d] = the same reads by their upstream and downstream rooms, the window positions on each side with a gap of at
+        most max_gap, n_primary, n_pair int64[n_mat]: primary reads with a secondary site, n_far int64[n_mat]: those with
+        g > max_gap, which are in neither histogram).  One pass over the original reads per batch of matrices, nothing per read
+        leaves the device.  Needs no scan handle."""
+        Ws = [_as_weights(W, "library_spacing") for W in Ws]
+        thresholds = [_as_threshold(t, "library_spacing") for t in thresholds]
+        prim_threshold = _as_threshold(prim_threshold, "library_spacing")
+        if len(Ws) != len(thresholds):
+            raise ValueError(f"library_spacing: {len(Ws)} matrices, {len(thresholds)} thresholds")
+        if isinstance(prim_width, bool) or int(prim_width) != prim_width or not 4 <= prim_width <= 31:
+            raise ValueError(f"library_spacing: the primary matrix has width {prim_width}, outside 4..31")
+        if isinstance(max_gap, bool) or int(max_gap) != max_gap or not 0 <= max_gap <= SPACING_MAX_GAP:
+            raise ValueError(f"library_spacing: max_gap {max_gap} outside 0 .. {SPACING_MAX_GAP}")
+        if not isinstance(primary, ReadScores) or primary.n_seq != self.n_seq:
+            raise ValueError(f"library_spacing: the primary must be the ReadScores of these {self.n_seq} reads")
+        n_mat, G = len(Ws), int(max_gap)
+        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
+        for m, W in enumerate(Ws):
+            if not 4 <= W.shape[1] <= 31:
+                raise ValueError(f"library_spacing: matrix {m} has width {W.shape[1]}, outside 4..31")
+            widths[m] = W.shape[1]
+            weights[m, :, :W.shape[1]] = W
+        thr = np.array(thresholds, np.int32).reshape(n_mat)
+        S, R = np.zeros((n_mat, 4, G + 1), np.uint64), np.zeros((n_mat, G + 2, G + 2), np.uint64)
+        pair, far, n_primary = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64), _ffi.i64(0)
+        check(_ffi.lib().kmap_readscore_spacing_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq,
+                                                            primary.score.ptr, primary.loc.ptr, primary.strand.ptr, int(prim_width),
+                                                            prim_threshold, n_mat, ptr(widths), ptr(weights), ptr(thr), int(bool(revcom)),
+                                                            G, ptr(S), ptr(R), C.byref(n_primary), ptr(pair), ptr(far), None))
+        return S.astype(np.int64), R.astype(np.int64), n_primary.value, pair, far
 
     def shuffled(self, klet=2, seed=0):
         """a new resident read set: every maximal run of valid bases of the ORIGINAL reads (inval_orig; a mask() before does not
