@@ -347,6 +347,29 @@ int kmap_readscore_spacing_library_dev(const uint32_t *codes_dev, const uint16_t
                                        int64_t *n_primary /* host, one */, int64_t *n_pair /* host, n_mat */,
                                        int64_t *n_far /* host, n_mat */, void *stream);
 
+/* ---- which reads hold a site of which matrix of a library, as bit rows, and how many reads every pair of rows shares
+ * (motif_cooccurrence; csrc/pwm_presence.hip, csrc/bit_pairs.hip) -- not in the reference.  Matrices, batches
+ * and argument rules are kmap_readscore_library_dev's.  Read r is present under matrix m when its best window
+ * (kmap_readscore_packed_dev's score) scores thresholds[m] or more; a read without a valid window is never present, whatever the
+ * threshold.  Bit r & 63 (least significant first) of planes_dev[m n_words + (r >> 6)] is that flag, the bits behind n_seq in the
+ * last word are 0; planes_dev is the caller's device array of n_mat x n_words words, every word of it is written.  n_present[m] =
+ * the popcount of row m.  Blocking (one synchronisation per call); integer maxima, ballots and counts only, so two calls give the
+ * same bits; scratch memory only, no handle.  KMAP_E_INVAL: a width outside 4..31, a weight of 2^31 / 31 or more in magnitude or
+ * behind the width, a negative size, n_words other than (n_seq + 63) / 64, a NULL array.  n_mat == 0 writes nothing; n_seq == 0
+ * gives rows without words and zero counts, n == 0 zero rows. */
+int kmap_presence_library_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
+                              const int64_t *borders_dev, int64_t n_seq,
+                              int n_mat, const int32_t *widths /* host */, const int32_t *weights /* host, n_mat x [4][32] */,
+                              const int32_t *thresholds /* host, n_mat */, int revcom,
+                              uint64_t *planes_dev /* n_mat x n_words, caller's */, int64_t n_words,
+                              int64_t *n_present /* host, n_mat */, void *stream);
+/* pairs_host[i n_mat + j] = sum over w of popcount(planes_dev[i n_words + w] & planes_dev[j n_words + w]), uint64: symmetric, the
+ * diagonal holds the row popcounts.  Any bit matrix is a legal input.  Blocking; integer sums only, so two calls give the same
+ * numbers; scratch memory only, no handle.  n_mat above 4096: KMAP_E_UNSUP; a negative size or a NULL array: KMAP_E_INVAL.
+ * n_mat == 0 writes nothing; n_words == 0 gives zeros. */
+int kmap_bitrows_pair_counts_dev(const uint64_t *planes_dev, int n_mat, int64_t n_words,
+                                 uint64_t *pairs_host /* n_mat x n_mat */, void *stream);
+
 /* ---- count matrices against a library of count matrices (match_motifs; csrc/motif_match.hip) -- not in the
  * reference.  A motif is a run of quantised columns: 4 x uint16 (A C G T, rint(1024 f), 0..1024) = 8 bytes per column, the columns of
  * a set of motifs behind one another in one device array; the reverse complement of a motif is read from the same columns.  Column

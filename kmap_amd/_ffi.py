@@ -115,6 +115,8 @@ _SIGS = {
     "kmap_readscore_sites_library_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]),
     "kmap_readscore_spacing_library_dev": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp,
                                                  vp, vp]),
+    "kmap_presence_library_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp]),
+    "kmap_bitrows_pair_counts_dev": (i32, [vp, i32, i64, vp, vp]),
     "kmap_match_hist_dev": (i32, [vp, i64, vp, i64, i32, vp, vp]),
     "kmap_match_tables_dev": (i32, [vp, i64, i64, i32, vp, vp, vp, vp, vp, i64, vp]),
     "kmap_match_pairs_dev": (i32, [vp, i64, i32, vp, vp, vp, vp, vp, i64, vp, i64, i32, vp, vp, i32, i32, vp, vp, vp]),

@@ -20,7 +20,9 @@ where in the reads the best site of every motif of a library lies: the sites wit
 placed uniformly, the half-width with the largest z, ranked, with q-values, no control needed (centrality.py), and `motif_spacing`,
 at which distance, on which side and on which relative strand of a primary motif's site the best non-overlapping site of every motif
 of a library lies: pair reads per (side, strand, gap) bin against a uniformly placed site, a Poisson tail for the best bin, ranked,
-with q-values (spacing.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+with q-values (spacing.py).  An eleventh, `motif_cooccurrence`, asks which pairs of motifs of a library share reads more or less often
+than their own frequencies predict: one presence bit per motif and read, the shared reads of all pairs counted on the GPU, a
+hypergeometric z per pair, two-sided p-values and q-values (cooccurrence.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -310,6 +312,35 @@ def motif_spacing(res_dir, primary_file, library_file, primary_name=None, p_valu
     from .spacing import _motif_spacing
     _motif_spacing(res_dir, primary_file, list(library_file), primary_name, p_value, primary_min_score, min_score, pseudocount,
                    nsites_default, revcom_mode, max_gap, min_pairs, top_hist, output_dir)
+
+
+@cli.command(name="motif_cooccurrence")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--library_file", type=str, required=True, multiple=True,
+              help="motif library: a MEME minimal text file, a 4 x w base-count matrix CSV (as for evaluate_pwm), or a directory of "
+                   "*.meme and *.csv files; may be given several times")
+@click.option("--control_fasta_file", type=str, default=None, required=False,
+              help="FASTA file of control reads: every written pair's shared count is compared with theirs (optional)")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="a read holds a motif when its best window reaches scan_pwm's threshold of this p-value (per strand and per position)")
+@click.option("--min_score", type=float, default=None, required=False,
+              help="score threshold in bits; replaces the threshold derived from --p_value")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base)")
+@click.option("--nsites_default", type=int, default=20, required=False,
+              help="sites behind a MEME motif without nsites= (its probabilities become counts of this many sites)")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="score both strands and keep the better one (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--min_expected", type=float, default=5.0, required=False,
+              help="a pair is tested when the expected shared count, and either motif's reads beyond it, are at least this")
+@click.option("--top_n", type=int, default=1000, required=False,
+              help="rows of cooccurrence_pairs.csv: the tested pairs with the largest |z|; 0 writes every pair")
+@click.option("--write_matrix", is_flag=True, default=False, help="also write the matrix of shared read counts, pair_counts.tsv")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: motif_cooccurrence in res_dir)")
+def motif_cooccurrence(res_dir, library_file, control_fasta_file=None, p_value=1e-4, min_score=None, pseudocount=1.0, nsites_default=20,
+                       revcom_mode=None, min_expected=5.0, top_n=1000, write_matrix=False, output_dir=None):
+    from .cooccurrence import _motif_cooccurrence
+    _motif_cooccurrence(res_dir, list(library_file), control_fasta_file, p_value, min_score, pseudocount, nsites_default, revcom_mode,
+                        min_expected, top_n, write_matrix, output_dir)
 
 
 @cli.command(name="shuffle_reads")

@@ -19,6 +19,8 @@
 //   * LDS budget: static LDS, 24 chunk tables and 8 matrices per batch -- 48 KB of tables with RC, 50.5 KB
 //     in all, so three blocks share a CU's 160 KB.  Unmeasured against the alternative (dynamic LDS, up to ~70 chunks, one block
 //     per CU).
+//   * pwm_library_key_batches (pwm_internal.h): the batching and the scoring launch as a host function that hands every batch's
+//     keys to a callback; the histogram entry point below and pwm_presence.hip's presence planes are its two callers.
 #include <numeric>
 #include <vector>
 
@@ -223,6 +225,70 @@ __global__ __launch_bounds__(LB_HIST_TPB) void library_hist_kernel(const unsigne
 
 }  // namespace
 
+// ---- the batch pass as other files reach it (pwm_internal.h) -----------------------------------------------------------------------
+
+int pwm_library_check(const char *who, int n_mat, const int32_t *widths, const int32_t *weights) {
+    KMAP_REQUIRE(widths && weights, "%s: null pointer", who);
+    for (int m = 0; m < n_mat; ++m) {
+        KMAP_REQUIRE(widths[m] >= 4 && widths[m] <= 31, "%s: width=%d of matrix %d outside 4..31", who, widths[m], m);
+        for (int e = 0; e < 128; ++e) {
+            const int32_t v = weights[(size_t)m * 128 + e];
+            KMAP_REQUIRE(v > -LB_MAX_WEIGHT && v < LB_MAX_WEIGHT, "%s: a weight of matrix %d is 2^31 / 31 or more: a window's score must fit int32", who, m);
+            KMAP_REQUIRE((e & 31) < widths[m] || v == 0, "%s: matrix %d has a weight behind its width %d", who, m, widths[m]);
+        }
+    }
+    return KMAP_OK;
+}
+
+int pwm_library_key_batches(const char *who, const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, const int64_t *borders_dev,
+                            int64_t n_seq, int n_mat, const int32_t *widths, const int32_t *weights, int revcom, hipStream_t st,
+                            const std::function<int(const LibKeys &)> &on_batch) {
+    const int64_t n_data = (n + 15) >> 4, n_tiles = (n_data + PW_TILE_GROUPS - 1) / PW_TILE_GROUPS;   // groups of 16 positions; wave tiles
+    // persistent blocks: as many as are resident at once (registers and LDS decide; the tables are built once per block)
+    int dev = 0, cus = 0, per_cu = 0;
+    KMAP_CHECK_HIP(hipGetDevice(&dev));
+    KMAP_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (revcom) KMAP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, readscore_multi_kernel<true>, PW_TPB, 0));
+    else KMAP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, readscore_multi_kernel<false>, PW_TPB, 0));
+    KMAP_REQUIRE(cus > 0 && per_cu > 0, "%s: no block of the scoring kernel fits a compute unit", who);
+    const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + PW_WAVES - 1) / PW_WAVES, (int64_t)cus * per_cu);
+
+    // by width (ties: the caller's order), so that a batch holds matrices of similar chunk counts
+    std::vector<int> order(n_mat);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return widths[a] < widths[b]; });
+
+    int32_t *weights_dev = nullptr;
+    KMAP_TRY(kmap_scratch((void **)&weights_dev, (size_t)n_mat * 512, st, KMAP_SLOT_C));
+    KMAP_CHECK_HIP(hipMemcpyAsync(weights_dev, weights, (size_t)n_mat * 512, hipMemcpyHostToDevice, st));
+    unsigned int *key = nullptr;
+    KMAP_TRY(kmap_scratch((void **)&key, (size_t)std::min(n_mat, LB_MAX_MAT) * (size_t)n_seq * 4, st, KMAP_SLOT_A));
+
+    for (int first = 0; first < n_mat;) {
+        LibBatch bt = {};
+        int chunks = 0;
+        while (first + bt.n_mat < n_mat && bt.n_mat < LB_MAX_MAT) {
+            const int m = order[first + bt.n_mat], nch = (widths[m] + 3) / 4, j = bt.n_mat;
+            if (chunks + nch > LB_MAX_CHUNKS) break;
+            bt.src[j] = m;
+            bt.width[j] = widths[m];
+            bt.chunk0[j] = chunks;
+            chunks += nch;
+            ++bt.n_mat;
+        }                                              // n_mat >= 1: one matrix has 8 chunks at the most
+        KMAP_CHECK_HIP(hipMemsetAsync(key, 0, (size_t)bt.n_mat * (size_t)n_seq * 4, st));
+        with_bool(revcom, [&](auto rc) {
+            readscore_multi_kernel<decltype(rc)::value><<<grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, n_data, n_tiles, weights_dev,
+                                                                                 bt, borders_dev, n_seq, key);
+        });
+        KMAP_CHECK_HIP(hipGetLastError());
+        const LibKeys keys = {bt.n_mat, bt.src, key};
+        KMAP_TRY(on_batch(keys));
+        first += bt.n_mat;
+    }
+    return KMAP_OK;
+}
+
 extern "C" {
 
 int kmap_readscore_library_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, const int64_t *borders_dev,
@@ -240,11 +306,7 @@ int kmap_readscore_library_dev(const uint32_t *codes_dev, const uint16_t *inval_
             kmap_set_error("readscore_library: %lld bins for matrix %d, more than 2^22", (long long)n_bins[m], m);
             return KMAP_E_UNSUP;
         }
-        for (int e = 0; e < 128; ++e) {
-            const int32_t v = weights[(size_t)m * 128 + e];
-            KMAP_REQUIRE(v > -LB_MAX_WEIGHT && v < LB_MAX_WEIGHT, "readscore_library: a weight of matrix %d is 2^31 / 31 or more: a window's score must fit int32", m);
-            KMAP_REQUIRE((e & 31) < widths[m] || v == 0, "readscore_library: matrix %d has a weight behind its width %d", m, widths[m]);
-        }
+        KMAP_TRY(pwm_library_check("readscore_library", 1, widths + m, weights + (size_t)m * 128));
         total_bins += (size_t)n_bins[m];
     }
     KMAP_REQUIRE(hist_host || total_bins == 0, "readscore_library: null histogram");
@@ -255,77 +317,43 @@ int kmap_readscore_library_dev(const uint32_t *codes_dev, const uint16_t *inval_
     KMAP_REQUIRE(codes_dev && inval_dev && borders_dev, "readscore_library: null pointer");
     hipStream_t st = as_stream(stream);
 
-    const int64_t n_data = (n + 15) >> 4, n_tiles = (n_data + PW_TILE_GROUPS - 1) / PW_TILE_GROUPS;   // groups of 16 positions; wave tiles
-    // persistent blocks: as many as are resident at once (registers and LDS decide; the tables are built once per block)
-    int dev = 0, cus = 0, per_cu = 0;
-    KMAP_CHECK_HIP(hipGetDevice(&dev));
-    KMAP_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (revcom) KMAP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, readscore_multi_kernel<true>, PW_TPB, 0));
-    else KMAP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, readscore_multi_kernel<false>, PW_TPB, 0));
-    KMAP_REQUIRE(cus > 0 && per_cu > 0, "readscore_library: no block of the scoring kernel fits a compute unit");
-    const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + PW_WAVES - 1) / PW_WAVES, (int64_t)cus * per_cu);
-
-    // by width (ties: the caller's order), so that a batch holds matrices of similar chunk counts
-    std::vector<int> order(n_mat);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return widths[a] < widths[b]; });
     std::vector<size_t> host_off(n_mat);               // the matrix's first bin in hist_host
     for (size_t m = 0, at = 0; m < (size_t)n_mat; at += (size_t)n_bins[m], ++m) host_off[m] = at;
-
-    int32_t *weights_dev = nullptr;
-    KMAP_TRY(kmap_scratch((void **)&weights_dev, (size_t)n_mat * 512, st, KMAP_SLOT_C));
-    KMAP_CHECK_HIP(hipMemcpyAsync(weights_dev, weights, (size_t)n_mat * 512, hipMemcpyHostToDevice, st));
-    unsigned int *key = nullptr;
-    KMAP_TRY(kmap_scratch((void **)&key, (size_t)std::min(n_mat, LB_MAX_MAT) * (size_t)n_seq * 4, st, KMAP_SLOT_A));
     KMAP_TRY(kmap_allow_lds((const void *)library_hist_kernel, (int)(LB_HIST_LDS_BINS * 4)));
 
     std::vector<unsigned long long> back;
-    for (int first = 0; first < n_mat;) {
-        LibBatch bt = {};
+    return pwm_library_key_batches("readscore_library", codes_dev, inval_dev, n, borders_dev, n_seq, n_mat, widths, weights, revcom, st,
+                                   [&](const LibKeys &keys) -> int {
         LibHist hs = {};
-        int chunks = 0;
         int64_t words = 0, lds_bins = 1;
-        while (first + bt.n_mat < n_mat && bt.n_mat < LB_MAX_MAT) {
-            const int m = order[first + bt.n_mat], nch = (widths[m] + 3) / 4, j = bt.n_mat;
-            if (chunks + nch > LB_MAX_CHUNKS) break;
-            bt.src[j] = m;
-            bt.width[j] = widths[m];
-            bt.chunk0[j] = chunks;
-            chunks += nch;
+        for (int j = 0; j < keys.n_mat; ++j) {
+            const int m = keys.src[j];
             hs.lds[j] = n_bins[m] <= LB_HIST_LDS_BINS;
             hs.lo[j] = lo[m];
             hs.n_bins[j] = n_bins[m];
             hs.off[j] = words;
             words += 2 + n_bins[m];
             if (hs.lds[j]) lds_bins = std::max(lds_bins, n_bins[m]);
-            ++bt.n_mat;
         }
-        hs.n_mat = bt.n_mat;                           // >= 1: one matrix has 8 chunks at the most
+        hs.n_mat = keys.n_mat;
         unsigned long long *acc = nullptr;
         KMAP_TRY(kmap_scratch((void **)&acc, (size_t)words * 8, st, KMAP_SLOT_B));
         KMAP_CHECK_HIP(hipMemsetAsync(acc, 0, (size_t)words * 8, st));
-        KMAP_CHECK_HIP(hipMemsetAsync(key, 0, (size_t)bt.n_mat * (size_t)n_seq * 4, st));
-        with_bool(revcom, [&](auto rc) {
-            readscore_multi_kernel<decltype(rc)::value><<<grid, PW_TPB, 0, st>>>(codes_dev, inval_dev, n_data, n_tiles, weights_dev,
-                                                                                 bt, borders_dev, n_seq, key);
-        });
-        KMAP_CHECK_HIP(hipGetLastError());
-        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for(n_seq, LB_HIST_TPB), LB_HIST_BLOCKS / bt.n_mat));
-        library_hist_kernel<<<dim3(gx, (unsigned)bt.n_mat), LB_HIST_TPB, (size_t)lds_bins * 4, st>>>(key, n_seq, hs, acc);
+        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for(n_seq, LB_HIST_TPB), LB_HIST_BLOCKS / keys.n_mat));
+        library_hist_kernel<<<dim3(gx, (unsigned)keys.n_mat), LB_HIST_TPB, (size_t)lds_bins * 4, st>>>(keys.key, n_seq, hs, acc);
         KMAP_CHECK_HIP(hipGetLastError());
         back.resize((size_t)words);
         KMAP_CHECK_HIP(hipMemcpyAsync(back.data(), acc, (size_t)words * 8, hipMemcpyDeviceToHost, st));
         KMAP_CHECK_HIP(hipStreamSynchronize(st));      // once per batch
-        for (int j = 0; j < bt.n_mat; ++j) {
-            const int m = bt.src[j];
+        for (int j = 0; j < keys.n_mat; ++j) {
+            const int m = keys.src[j];
             const unsigned long long *a = back.data() + hs.off[j];
             n_outside[m] = (int64_t)a[0];
             n_scored[m] = n_seq - (int64_t)a[1];
             if (n_bins[m]) memcpy(hist_host + host_off[m], a + 2, (size_t)n_bins[m] * 8);
         }
-        first += bt.n_mat;
-    }
-    return KMAP_OK;
+        return KMAP_OK;
+    });
 }
 
 }  // extern "C"

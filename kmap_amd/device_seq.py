@@ -23,6 +23,8 @@ LIBRARY_BATCH, LIBRARY_BATCH_CHUNKS = 8, 24    # csrc/pwm_library.hip: a batch i
 LIBRARY_LDS_BINS, LIBRARY_MAX_BINS = 32768, 1 << 22      # ranges up to the first are counted in block-private bins; the second is the limit
 SITES_MAX_LEN = 1 << 20                        # csrc/pwm_sites.hip: the longest read library_sites makes histograms for
 SPACING_MAX_GAP = 511                          # csrc/pwm_spacing.hip: the largest gap library_spacing makes histograms for
+# csrc/bit_pairs.hip: the words of a staging step, the fewest words of a block's slice, the most rows pair_counts takes
+BIT_PAIRS_K, BIT_PAIRS_MIN_SLICE, BIT_PAIRS_MAX_ROWS = 32, 128, 4096
 
 
 def _as_threshold(t, who):
@@ -354,6 +356,34 @@ class DeviceSeq:
                                                             G, ptr(S), ptr(R), C.byref(n_primary), ptr(pair), ptr(far), None))
         return S.astype(np.int64), R.astype(np.int64), n_primary.value, pair, far
 
+    def library_presence(self, Ws, thresholds, revcom):
+        """For every weight matrix of Ws (int32 [4, width], widths may differ) which reads hold a site: read r is present under
+        matrix m when its best window (read_scores') scores thresholds[m] or more; a read without a valid window never is
+        (csrc/pwm_presence.hip).  Returns a PresencePlanes: one bit per (matrix, read) in HBM and n_present
+        int64[n_mat].  One pass over the original reads per batch of matrices, nothing per read leaves the device.  Needs no scan
+        handle."""
+        Ws = [_as_weights(W, "library_presence") for W in Ws]
+        thresholds = [_as_threshold(t, "library_presence") for t in thresholds]
+        if len(Ws) != len(thresholds):
+            raise ValueError(f"library_presence: {len(Ws)} matrices, {len(thresholds)} thresholds")
+        n_mat = len(Ws)
+        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
+        for m, W in enumerate(Ws):
+            if not 4 <= W.shape[1] <= 31:
+                raise ValueError(f"library_presence: matrix {m} has width {W.shape[1]}, outside 4..31")
+            widths[m] = W.shape[1]
+            weights[m, :, :W.shape[1]] = W
+        thr = np.array(thresholds, np.int32).reshape(n_mat)
+        out = PresencePlanes(n_mat, self.n_seq)
+        try:
+            check(_ffi.lib().kmap_presence_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,
+                                                       ptr(widths), ptr(weights), ptr(thr), int(bool(revcom)), out.planes.ptr,
+                                                       out.n_words, ptr(out.n_present), None))
+        except BaseException:
+            out.close()
+            raise
+        return out
+
     def shuffled(self, klet=2, seed=0):
         """a new resident read set: every maximal run of valid bases of the ORIGINAL reads (inval_orig; a mask() before does not
         count) shuffled so that its base counts (klet 1) or its first base and dinucleotide counts (klet 2) stay (csrc/shuffle.hip,
@@ -433,6 +463,40 @@ class ReadScores:
     def close(self):
         for b in (self.score, self.loc, self.strand):
             b.free()
+
+
+def bitrows_pair_counts(planes, n_mat, n_words):
+    """int64 [n_mat, n_mat]: C[i][j] = the bits that rows i and j of the bit matrix `planes` (a DeviceBuffer of uint64 [n_mat,
+    n_words]) share; symmetric, the diagonal holds the row popcounts (csrc/bit_pairs.hip)"""
+    n_mat, n_words = int(n_mat), int(n_words)
+    if not 0 <= n_mat <= BIT_PAIRS_MAX_ROWS or n_words < 0:
+        raise ValueError(f"pair_counts: {n_mat} rows of {n_words} words, 0 .. {BIT_PAIRS_MAX_ROWS} rows are supported")
+    pairs = np.zeros((n_mat, n_mat), np.uint64)
+    check(_ffi.lib().kmap_bitrows_pair_counts_dev(planes.ptr, n_mat, n_words, ptr(pairs), None))
+    return pairs.astype(np.int64)
+
+
+class PresencePlanes:
+    """DeviceSeq.library_presence's result: planes uint64 [n_mat, n_words] in HBM, bit r & 63 (least significant first) of word
+    r >> 6 of row m = read r is present under matrix m, the bits behind n_seq are 0; n_present int64[n_mat] = the row popcounts."""
+
+    def __init__(self, n_mat, n_seq):
+        self.n_mat, self.n_seq, self.n_words = int(n_mat), int(n_seq), (int(n_seq) + 63) // 64
+        self.planes = _ffi.DeviceBuffer(max(self.n_mat * self.n_words, 1) * 8)
+        self.n_present = np.zeros(self.n_mat, np.int64)
+
+    def pair_counts(self):
+        """int64 [n_mat, n_mat]: C[i][j] = reads present under both matrix i and matrix j; C[i][i] = n_present[i]"""
+        return bitrows_pair_counts(self.planes, self.n_mat, self.n_words)
+
+    def fetch(self):
+        """the planes as a uint64 [n_mat, n_words] numpy array"""
+        out = self.planes.to_numpy(np.uint64, (self.n_mat, self.n_words))
+        _ffi.sync()
+        return out
+
+    def close(self):
+        self.planes.free()
 
 
 class ScanHits:
