@@ -318,6 +318,23 @@ int kmap_readscore_sites_library_dev(const uint32_t *codes_dev, const uint16_t *
                                      uint64_t *len_hist_host /* n_mat x (max_len + 1) */,
                                      int64_t *n_sites /* host, n_mat */, int64_t *n_too_long /* host, n_mat */, void *stream);
 
+/* ---- one refinement step for a batch of weight matrices (discover_pwms; csrc/pwm_sites.hip) -- not in the
+ * reference.  Matrices, batches and argument rules are kmap_readscore_sites_library_dev's, and so are the site reads: a read whose
+ * best window (the largest score, on a tie the smallest loc) scores thresholds[m] or more; that window is the read's selected
+ * window.  Per matrix this is kmap_refine_counts_packed_dev with select_best 1, without *n_hits: counts_host[(m 4 + b) 32 + j] =
+ * the number of selected windows whose oriented base j is b -- window base j on '+', 3 - (window base widths[m] - 1 - j) on '-';
+ * '-' only when rc > fwd, never without revcom --, the cells behind the width 0; n_selected[m] = the site reads (= every column
+ * sum), n_minus[m] = those on '-'.  Blocking (one synchronisation per batch); integer maxima and counts only, so two calls give the
+ * same numbers; scratch memory only, no handle.  KMAP_E_INVAL: a width outside 4..31, a weight of 2^31 / 31 or more in magnitude or
+ * behind the width, a negative size, n_seq of 2^32 or more, a NULL array.  n_mat == 0 writes nothing; n_seq == 0 or n == 0 gives
+ * zeros. */
+int kmap_readscore_counts_library_dev(const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
+                                      const int64_t *borders_dev, int64_t n_seq,
+                                      int n_mat, const int32_t *widths /* host */, const int32_t *weights /* host, n_mat x [4][32] */,
+                                      const int32_t *thresholds /* host, n_mat */, int revcom,
+                                      uint64_t *counts_host /* n_mat x [4][32] */,
+                                      int64_t *n_selected /* host, n_mat */, int64_t *n_minus /* host, n_mat */, void *stream);
+
 /* ---- at which distance and in which orientation the best site of every matrix of a library lies from a primary matrix's site
  * (motif_spacing; csrc/pwm_spacing.hip) -- not in the reference.  Matrices, batches and argument rules are
  * kmap_readscore_library_dev's.  prim_score_dev / prim_loc_dev / prim_strand_dev are kmap_readscore_packed_dev's three arrays for

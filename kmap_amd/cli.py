@@ -22,7 +22,10 @@ at which distance, on which side and on which relative strand of a primary motif
 of a library lies: pair reads per (side, strand, gap) bin against a uniformly placed site, a Poisson tail for the best bin, ranked,
 with q-values (spacing.py).  An eleventh, `motif_cooccurrence`, asks which pairs of motifs of a library share reads more or less often
 than their own frequencies predict: one presence bit per motif and read, the shared reads of all pairs counted on the GPU, a
-hypergeometric z per pair, two-sided p-values and q-values (cooccurrence.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+hypergeometric z per pair, two-sided p-values and q-values (cooccurrence.py).  A twelfth, `discover_pwms`, makes the library the others
+consume: the k-mers most enriched against control reads become seeds, every seed grows from the Hamming ball around it into a
+count matrix by refine_pwm's iteration -- all seeds in lockstep, one batched counting pass over the reads per round --, and the
+matrices are evaluated against the control and grouped into families, one representative each (discover.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -341,6 +344,34 @@ def motif_cooccurrence(res_dir, library_file, control_fasta_file=None, p_value=1
     from .cooccurrence import _motif_cooccurrence
     _motif_cooccurrence(res_dir, list(library_file), control_fasta_file, p_value, min_score, pseudocount, nsites_default, revcom_mode,
                         min_expected, top_n, write_matrix, output_dir)
+
+
+@cli.command(name="discover_pwms")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--control_fasta_file", type=str, required=True,
+              help="FASTA file of the control reads (input DNA, flanks, round 0, shuffled reads); counted and scored like the reads of res_dir")
+@click.option("--seed_len", type=int, default=8, required=False, help="length of the seed k-mers (at least 4; seed_len + 2 x flank <= 31)")
+@click.option("--n_seeds", type=int, default=64, required=False, help="seeds: the k-mers with the largest z > 0 against the control, 1..1024")
+@click.option("--seed_mismatches", type=int, default=1, required=False,
+              help="the first iteration selects the windows within this many mismatches of the seed (0 .. seed_len - 1)")
+@click.option("--seed_count", type=int, default=20, required=False, help="the count a seed's matrix holds at the k-mer's base of every column")
+@click.option("--flank", type=int, default=2, required=False, help="empty columns added on each side of a seed")
+@click.option("--min_count", type=int, default=2, required=False, help="smallest foreground count of a seed k-mer")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="hit threshold of the later iterations and of the evaluation, as scan_pwm's: per strand and per position")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base); > 0")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="count, score and match on both strands (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--max_iter", type=int, default=20, required=False, help="largest number of iterations")
+@click.option("--min_overlap", type=int, default=5, required=False, help="fewest columns two matrices overlap in when they are matched")
+@click.option("--family_e_value", type=float, default=0.01, required=False,
+              help="two matrices are linked when each finds the other with an E-value of at most this")
+@click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: pwm_discovery in res_dir)")
+def discover_pwms(res_dir, control_fasta_file, seed_len=8, n_seeds=64, seed_mismatches=1, seed_count=20, flank=2, min_count=2,
+                  p_value=1e-4, pseudocount=1.0, revcom_mode=None, max_iter=20, min_overlap=5, family_e_value=0.01, output_dir=None):
+    from .discover import _discover_pwms
+    _discover_pwms(res_dir, control_fasta_file, seed_len, n_seeds, seed_mismatches, seed_count, flank, min_count, p_value, pseudocount,
+                   revcom_mode, max_iter, min_overlap, family_e_value, output_dir)
 
 
 @cli.command(name="shuffle_reads")

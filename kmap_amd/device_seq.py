@@ -317,6 +317,31 @@ class DeviceSeq:
                                                           ptr(Hlen), ptr(sites), ptr(too_long), None))
         return D.astype(np.int64), Hlen.astype(np.int64), sites, too_long
 
+    def library_counts(self, Ws, thresholds, revcom):
+        """One refinement step for every weight matrix of Ws (int32 [4, width], widths may differ): the count matrix of the site
+        reads' best windows (csrc/pwm_sites.hip).  Per matrix what pwm_counts(W, t, revcom,
+        select_best=True) returns without n_hits, from library_sites' one pass over the original reads per batch of matrices:
+        returns (list of int64[4, w_m]: C'[b][j] = selected windows whose oriented base j is b, n_selected int64[n_mat]: the site
+        reads, n_minus int64[n_mat]: those on '-').  Nothing per read leaves the device.  Needs no scan handle."""
+        Ws = [_as_weights(W, "library_counts") for W in Ws]
+        thresholds = [_as_threshold(t, "library_counts") for t in thresholds]
+        if len(Ws) != len(thresholds):
+            raise ValueError(f"library_counts: {len(Ws)} matrices, {len(thresholds)} thresholds")
+        n_mat = len(Ws)
+        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
+        for m, W in enumerate(Ws):
+            if not 4 <= W.shape[1] <= 31:
+                raise ValueError(f"library_counts: matrix {m} has width {W.shape[1]}, outside 4..31")
+            widths[m] = W.shape[1]
+            weights[m, :, :W.shape[1]] = W
+        thr = np.array(thresholds, np.int32).reshape(n_mat)
+        counts = np.zeros((n_mat, 4, 32), np.uint64)
+        n_sel, n_minus = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64)
+        check(_ffi.lib().kmap_readscore_counts_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,
+                                                           ptr(widths), ptr(weights), ptr(thr), int(bool(revcom)), ptr(counts),
+                                                           ptr(n_sel), ptr(n_minus), None))
+        return [counts[m, :, :int(widths[m])].astype(np.int64) for m in range(n_mat)], n_sel, n_minus
+
     def library_spacing(self, primary, prim_width, prim_threshold, Ws, thresholds, revcom, max_gap=150):
         """For every weight matrix of Ws (int32 [4, width], widths may differ) at which distance and in which orientation its best
         site lies from the primary matrix's site (csrc/pwm_spacing.hip).  `primary` is the ReadScores of the

@@ -148,6 +148,28 @@ class DeviceEnrich:
             pass
 
 
+# ---- counting and selection of one k-mer length (enrich_kmers and discover_pwms) --------------------------------------------------
+def count_both(fg_seq, ctl_seq, dc_f, dc_b, k, dedupe, revcom):
+    """reads and control counted at length k into dc_f / dc_b, both merged with revcom: (n_fg_uniq, Nf, Nb)"""
+    n_fg = fg_seq.count(dc_f, k, dedupe, revcom, use_work=False)
+    Nf = dc_f.total()
+    ctl_seq.count(dc_b, k, dedupe, revcom, use_work=False)       # merged like the foreground: the total and the ball masses
+    Nb = dc_b.total()
+    if max(Nf, Nb) > MAX_TOTAL or min(Nf, Nb) < 0:
+        raise ValueError(f"k={k}: totals {Nf} / {Nb} outside 0..2^52 - 1")
+    return n_fg, Nf, Nb
+
+
+def select_enriched(ctl_seq, dc_f, dc_b, en, k, dedupe, revcom, Nf, Nb, min_count, top_n):
+    """behind count_both: the device join, the z of every foreground k-mer with a count >= min_count and the exact selection of
+    the top_n best: (fetch()'s rows in rank order, n_control_uniq).  dc_b is counted again without the merge when revcom is set."""
+    n_ctl = ctl_seq.count(dc_b, k, dedupe, False, use_work=False) if revcom else dc_b.n_uniq     # B: unmerged, ascending
+    en.set_control(dc_b, revcom)
+    en.run(dc_f, Nf, Nb, min_count)
+    en.select(top_n)
+    return en.fetch(), n_ctl
+
+
 # ---- the verb -----------------------------------------------------------------------------------------------------------------
 def _enrich_kmers(res_dir, control_fasta_file, kmer_len=(), top_n=1000, min_count=2, pseudocount=1.0, conseq_file=None,
                   output_dir=None):
@@ -208,12 +230,7 @@ def _enrich_kmers(res_dir, control_fasta_file, kmer_len=(), top_n=1000, min_coun
         ctl_seq = DeviceSeq(*encode_fasta(str(control_fasta_file)))
         dc_f, dc_b, en = DeviceCounts(), DeviceCounts(), DeviceEnrich()
         for k in sorted(set(kmer_lens) | set(by_len)):          # both read sets are counted once per distinct length
-            n_fg = fg_seq.count(dc_f, k, dedupe, revcom, use_work=False)
-            Nf = dc_f.total()
-            ctl_seq.count(dc_b, k, dedupe, revcom, use_work=False)   # merged like the foreground: the total and the ball masses
-            Nb = dc_b.total()
-            if max(Nf, Nb) > MAX_TOTAL or min(Nf, Nb) < 0:
-                raise ValueError(f"k={k}: totals {Nf} / {Nb} outside 0..2^52 - 1")
+            n_fg, Nf, Nb = count_both(fg_seq, ctl_seq, dc_f, dc_b, k, dedupe, revcom)
             if k in by_len:
                 d = motif_def[k]
                 cands = np.array([kmer2hash(c) for c in by_len[k]], np.uint64)
@@ -221,11 +238,7 @@ def _enrich_kmers(res_dir, control_fasta_file, kmer_len=(), top_n=1000, min_coun
                 for c, x, y in zip(by_len[k], ma, mb):
                     masses[c] = (d, int(x), int(y), Nf, Nb)
             if k in kmer_lens:
-                n_ctl = ctl_seq.count(dc_b, k, dedupe, False, use_work=False) if revcom else dc_b.n_uniq   # B: unmerged, ascending
-                en.set_control(dc_b, revcom)
-                en.run(dc_f, Nf, Nb, min_count)
-                en.select(top_n)
-                kmers[k] = en.fetch()
+                kmers[k], n_ctl = select_enriched(ctl_seq, dc_f, dc_b, en, k, dedupe, revcom, Nf, Nb, min_count, top_n)
                 info.append(dict(k=k, dedupe=dedupe, revcom=revcom, n_fg_uniq=n_fg, n_control_uniq=n_ctl, Nf=Nf, Nb=Nb,
                                  min_count=min_count, n_eligible=en.n_eligible, n_written=en.n_sel))
     finally:
