@@ -192,8 +192,9 @@ int kmap_counts_presence_dev(kmap_counts *c, int k, void *nib_dev, void *stream)
 int kmap_counts_merge_presence_dev(kmap_counts *c, int k, const void *nib_dev, void *stream);
 int kmap_counts_finish_range(kmap_counts *c, int k, int merged, uint64_t first_bin, uint64_t n_bins, int64_t *n_uniq, void *stream);
 int kmap_counts_adopt_dev(kmap_counts *c, const void *uniq_dev, const void *cnt_dev, int64_t n_uniq, int k);
-/* planes_dev (optional, from kmap_pack_planes_dev): with it and k <= 16 the Hamming-ball test of all windows runs bit-sliced
- * over positions (csrc/bitslice.hip) instead of window by window; NULL keeps the per-window kernels.  Results are identical. */
+/* planes_dev (from kmap_pack_planes_dev): at k <= 16 the Hamming-ball test of all windows runs bit-sliced over positions
+ * (csrc/bitslice.hip) and needs it -- NULL is KMAP_E_INVAL, nothing written; k > 16 runs window by window and never reads it
+ * (NULL is fine).  In place on inval_dev: bits are ORed into its kmap_packed_groups(n) words, codes_dev is only read. */
 int kmap_mask_hamball_packed_dev(const uint32_t *codes_dev, uint16_t *inval_dev, int64_t n, int k, const uint64_t *cons,
                                  const int32_t *radius, int n_cons, const uint32_t *planes_dev, void *stream);
 /* positions [0, m) of the packed reads become invalid (bit 15 - i of group word g = position 16 g + i): what a consensus within its
