@@ -15,8 +15,8 @@ from pathlib import Path
 import numpy as np
 
 from .enrichment import enrich_z
-from .library import SKIPPED_HEADER, _field, _file_name, bh_qvalues, log10_p_of_z, rank_order, read_motif_library
-from .pwm import SCORE_UNIT, min_score_threshold, pwm_consensus, pwm_threshold, pwm_weights
+from .library import _file_name, bh_qvalues, load_library, log10_p_of_z, open_read_sets, rank_order, write_skipped
+from .pwm import SCORE_UNIT, min_score_threshold, pwm_consensus
 
 OUTPUT_DIR, RANK_FILE, SKIPPED_FILE, OFFSETS_FILE = "motif_centrality", "centrality_rank.csv", "skipped.csv", "site_offsets_{rank}_{name}.csv"
 RANK_HEADER = ("rank,name,altname,source,width,consensus,threshold,threshold_bits,n_sites,half_width_x2,half_width_bases,"
@@ -140,7 +140,7 @@ def _motif_centrality(res_dir, library_files, control_fasta_file=None, p_value=1
     touched or a file is written; motifs whose width lies outside 4..31 are listed in skipped.csv.  Under a torch.distributed
     launch rank 0 works alone.  Returns one dict per motif in rank order: best_region's fields plus motif, rank, threshold, D,
     Hlen, q_bh and, with a control, D_control, control_sites, control_in_region, z_vs_control."""
-    from .kmer_count import encode_fasta, load_array_pickle, load_config, rank0_only, result_paths
+    from .kmer_count import load_config, rank0_only, result_paths
     if not rank0_only():
         return None
     res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
@@ -158,41 +158,18 @@ def _motif_centrality(res_dir, library_files, control_fasta_file=None, p_value=1
     t_fixed = None if min_score is None else min_score_threshold(min_score)
     _, revcom = load_config(cfg_path, revcom_mode)
 
-    motifs, skipped, Ws, ts = [], [], [], []
-    for f in library_files:
-        for m in read_motif_library(f, nsites_default):
-            if m.skip is not None:
-                skipped.append(m)
-                continue
-            try:
-                W = pwm_weights(m.counts, pseudocount)
-                t = pwm_threshold(W, p_value)[0]
-            except ValueError as exc:
-                raise ValueError(f"{m.source}: motif {m.name}: {exc}") from None
-            motifs.append(m)
-            Ws.append(W)
-            ts.append(t if t_fixed is None else t_fixed)
-    if not motifs:
-        raise ValueError(f"motif_centrality: none of the {len(skipped)} motifs of the library can be scored "
-                         f"(the first: {skipped[0].name}: {skipped[0].skip})")
+    motifs, skipped, Ws, plans = load_library("motif_centrality", library_files, nsites_default, pseudocount, p_value, t_fixed)
+    ts = [p[0] for p in plans]
 
-    from .motif_discovery import DeviceSeq
-    fg_seq = DeviceSeq(load_array_pickle(seq_path), load_array_pickle(border_path))
-    ctl_seq, per_set = None, []
-    try:
-        if control_fasta_file is not None:
-            ctl_seq = DeviceSeq(*encode_fasta(str(control_fasta_file)))
-        for ds in (fg_seq, ctl_seq):
+    per_set = []
+    with open_read_sets(seq_path, border_path, control_fasta_file) as read_sets:
+        for ds in read_sets:
             if ds is not None:
                 D, Hlen, _, too_long = ds.library_sites(Ws, ts, revcom)
                 if np.any(np.asarray(too_long) != 0):
                     raise ValueError(f"motif_centrality: site reads of motif {motifs[int(np.nonzero(too_long)[0][0])].name} are longer "
                                      "than the longest read")
                 per_set.append((D, Hlen))
-    finally:
-        for h in (ctl_seq, fg_seq):
-            if h is not None:
-                h.close()
 
     control = len(per_set) == 2
     results = []
@@ -217,9 +194,7 @@ def _motif_centrality(res_dir, library_files, control_fasta_file=None, p_value=1
         for rank, st in enumerate(results):
             st["rank"] = rank
             fh.write(rank_line(rank, st["motif"], st["threshold"], st, control))
-    with open(out / SKIPPED_FILE, "w") as fh:
-        fh.write(SKIPPED_HEADER)
-        fh.write("".join(f"{m.name},{m.altname},{m.source},{_field(m.skip)}\n" for m in skipped))
+    write_skipped(out, skipped)
     for st in results[:int(top_hist)]:
         write_site_offsets(out / OFFSETS_FILE.format(rank=st["rank"], name=_file_name(st["motif"].name)), st["D"], st.get("D_control"))
     for st in results[:10]:

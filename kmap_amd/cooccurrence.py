@@ -19,8 +19,8 @@ from pathlib import Path
 import numpy as np
 
 from .enrichment import enrich_z
-from .library import SKIPPED_HEADER, _field, bh_qvalues, read_motif_library
-from .pwm import SCORE_UNIT, min_score_threshold, pwm_consensus, pwm_threshold, pwm_weights
+from .library import bh_qvalues, load_library, open_read_sets, write_skipped
+from .pwm import SCORE_UNIT, min_score_threshold, pwm_consensus
 
 OUTPUT_DIR, PAIRS_FILE, PRESENCE_FILE, SKIPPED_FILE, MATRIX_FILE = ("motif_cooccurrence", "cooccurrence_pairs.csv", "motif_presence.csv",
                                                                     "skipped.csv", "pair_counts.tsv")
@@ -190,7 +190,7 @@ def _motif_cooccurrence(res_dir, library_files, control_fasta_file=None, p_value
     touched or a file is written; motifs whose width lies outside 4..31 are listed in skipped.csv.  Under a torch.distributed launch
     rank 0 works alone.  Returns a dict: motifs, thresholds, n_reads, pair_counts, rows (pair_rows', in rank order), n_tests and,
     with a control, control_reads and control_pair_counts."""
-    from .kmer_count import encode_fasta, load_array_pickle, load_config, rank0_only, result_paths
+    from .kmer_count import load_config, rank0_only, result_paths
     if not rank0_only():
         return None
     res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
@@ -206,33 +206,14 @@ def _motif_cooccurrence(res_dir, library_files, control_fasta_file=None, p_value
     t_fixed = None if min_score is None else min_score_threshold(min_score)
     _, revcom = load_config(cfg_path, revcom_mode)
 
-    motifs, skipped, Ws, ts = [], [], [], []
-    for f in library_files:
-        for m in read_motif_library(f, nsites_default):
-            if m.skip is not None:
-                skipped.append(m)
-                continue
-            try:
-                W = pwm_weights(m.counts, pseudocount)
-                t = pwm_threshold(W, p_value)[0]
-            except ValueError as exc:
-                raise ValueError(f"{m.source}: motif {m.name}: {exc}") from None
-            motifs.append(m)
-            Ws.append(W)
-            ts.append(t if t_fixed is None else t_fixed)
-    if not motifs:
-        raise ValueError(f"motif_cooccurrence: none of the {len(skipped)} motifs of the library can be scored "
-                         f"(the first: {skipped[0].name}: {skipped[0].skip})")
+    motifs, skipped, Ws, plans = load_library("motif_cooccurrence", library_files, nsites_default, pseudocount, p_value, t_fixed)
+    ts = [p[0] for p in plans]
     if len(motifs) > MAX_MOTIFS:
         raise ValueError(f"motif_cooccurrence: {len(motifs)} motifs, more than {MAX_MOTIFS}")
 
-    from .motif_discovery import DeviceSeq
-    fg_seq = DeviceSeq(load_array_pickle(seq_path), load_array_pickle(border_path))
-    ctl_seq, per_set = None, []
-    try:
-        if control_fasta_file is not None:
-            ctl_seq = DeviceSeq(*encode_fasta(str(control_fasta_file)))
-        for ds in (fg_seq, ctl_seq):
+    per_set = []
+    with open_read_sets(seq_path, border_path, control_fasta_file) as read_sets:
+        for ds in read_sets:
             if ds is not None:
                 planes = ds.library_presence(Ws, ts, revcom)
                 try:
@@ -242,10 +223,6 @@ def _motif_cooccurrence(res_dir, library_files, control_fasta_file=None, p_value
                 finally:
                     planes.close()
                 per_set.append((C, int(ds.n_seq)))
-    finally:
-        for h in (ctl_seq, fg_seq):
-            if h is not None:
-                h.close()
 
     control = len(per_set) == 2
     (C, N), (Cc, Nc) = per_set[0], per_set[1] if control else (None, None)
@@ -253,9 +230,7 @@ def _motif_cooccurrence(res_dir, library_files, control_fasta_file=None, p_value
     out = res / OUTPUT_DIR if output_dir is None else Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
     write_tables(out, motifs, ts, rows, C, N, Cc, Nc, write_matrix)
-    with open(out / SKIPPED_FILE, "w") as fh:
-        fh.write(SKIPPED_HEADER)
-        fh.write("".join(f"{m.name},{m.altname},{m.source},{_field(m.skip)}\n" for m in skipped))
+    write_skipped(out, skipped)
     for rank, row in enumerate(rows[:10]):
         mi, mj = motifs[row["i"]], motifs[row["j"]]
         what = (f"z {row['z']:.6g} ({row['direction']}), log10 p {row['log10_p']:.2f}, exact {row['log10_p_exact']:.2f}, q {row['q_bh']:.3g}"

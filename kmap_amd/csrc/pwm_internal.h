@@ -4,11 +4,10 @@
 //           tile), for_each_hit, the ONE sparse traversal of pass A's hits that every later pass of scan and refine is a call of,
 //           and tile_read_starts, the reads of a wave tile for the two dense per-read passes
 //   host:   PwmPlan (an entry point's checks, the weights as a kernel argument, the launch geometry), pwm_pass_a (scratch, launch,
-//           exclusive scan of the tile counts, total), with_bool (a run-time flag as a template argument) and, at the end, the
-//           declarations of pwm_library.hip's batch pass for pwm_presence.hip
+//           exclusive scan of the tile counts, total), with_bool (a run-time flag as a template argument)
+// pwm_batch.h holds the batched dense pass of the library verbs (DESIGN.md sections 16, 18 to 20).
 #pragma once
 #include <algorithm>
-#include <functional>
 #include <type_traits>
 
 #include "common.h"
@@ -136,7 +135,7 @@ __device__ __forceinline__ int64_t find_read(const int64_t *__restrict__ borders
     return lo;
 }
 
-// ---- the reads of a wave tile: what the dense per-read passes share (pwm_readscore.hip, pwm_library.hip) -----------------------------
+// ---- the reads of a wave tile: what the dense per-read passes share (pwm_readscore.hip, pwm_batch.h) -----------------------------
 constexpr int RS_TILE_POS = PW_TILE_GROUPS * 16;      // 1024 positions per wave tile
 
 // the wave's own LDS words: what its lanes wrote (stores, atomics) before is what they read after; no block barrier -- the waves of
@@ -305,20 +304,3 @@ inline int pwm_pass_a(const PwmPlan &pl, const uint32_t *codes, const uint16_t *
 }
 
 }  // namespace
-
-// ---- pwm_library.hip's batch pass for other files (pwm_presence.hip): readscore_multi_kernel exists once ------------------------------
-// the argument rules of kmap_readscore_library_dev's matrices (`who` = the caller's prefix in the messages): KMAP_E_INVAL for a width
-// outside 4..31, a weight of 2^31 / 31 or more in magnitude or behind the width, a NULL array
-int pwm_library_check(const char *who, int n_mat, const int32_t *widths, const int32_t *weights);
-// One batch's keys as the scoring kernel left them in scratch slot A: key[j n_seq + r] of the batch's matrix j = the caller's matrix
-// src[j]; the best score of read r with the sign bit flipped, 0 = no valid window.  They are valid on the stream until on_batch returns.
-struct LibKeys {
-    int n_mat;
-    const int *src;
-    const unsigned int *key;
-};
-// Checked matrices, n > 0, n_seq > 0, n_mat > 0: batches them (8 matrices, 24 chunk tables), scores a batch on `st` and calls
-// on_batch, which enqueues its own work on `st` behind the kernel; no synchronisation of its own.  Uses the scratch slots A and C.
-int pwm_library_key_batches(const char *who, const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n, const int64_t *borders_dev,
-                            int64_t n_seq, int n_mat, const int32_t *widths, const int32_t *weights, int revcom, hipStream_t st,
-                            const std::function<int(const LibKeys &)> &on_batch);

@@ -1,6 +1,7 @@
 // pwm_presence.hip -- which reads hold a site of which matrix of a library, one bit per (matrix, read) (motif_cooccurrence, DESIGN.md
-// section 20).  The scoring is pwm_library.hip's batch pass, reached through pwm_library_key_batches (pwm_internal.h): it leaves the
-// 32-bit keys of a batch -- the best score of every read with the sign bit flipped, 0 = no valid window -- in scratch.  Behind it:
+// section 20).  The scoring is pwm_batch.h's batched pass with the score alone as the key (ScoreKey), as pwm_library.hip runs it: it
+// leaves the 32-bit keys of a batch -- the best score of every read with the sign bit flipped, 0 = no valid window -- in scratch.
+// Behind it:
 //   * presence_kernel: blockIdx.y = the matrix of the batch, the waves stride over the 64-read words of its row.  A lane reads one
 //     key, compares it with the flipped threshold (unsigned order of flipped keys = signed order of scores; key 0 is never present,
 //     whatever the threshold), the wave ballots, lane 0 writes the word with a plain vector store -- every word of the row is
@@ -11,18 +12,17 @@
 #include <vector>
 
 #include "common.h"
-#include "pwm_internal.h"
+#include "pwm_batch.h"
 
 namespace {
 
 constexpr int PR_TPB = 256;
 constexpr int PR_WAVES = PR_TPB / KMAP_WAVE;
-constexpr int PR_MAX_MAT = 8;            // pwm_library.hip's LB_MAX_MAT
 constexpr int PR_BLOCKS = 2048;          // blocks of one launch, over all matrices of the batch
 
 struct PresBatch {
-    uint32_t tkey[PR_MAX_MAT];           // the threshold with the sign bit flipped
-    int src[PR_MAX_MAT];                 // the matrix's row in the planes and in n_present
+    uint32_t tkey[PB_MAX_MAT];           // the threshold with the sign bit flipped
+    int src[PB_MAX_MAT];                 // the matrix's row in the planes and in n_present
 };
 
 __global__ __launch_bounds__(PR_TPB) void presence_kernel(const unsigned int *__restrict__ key, int64_t n_seq, int64_t n_words, PresBatch pb,
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(PR_TPB) void presence_kernel(const unsigned int *__
     uint32_t tkey = 0;
     int src = 0;
 #pragma unroll
-    for (int i = 0; i < PR_MAX_MAT; ++i)
+    for (int i = 0; i < PB_MAX_MAT; ++i)
         if (i == j) {                      // uniform
             tkey = pb.tkey[i];
             src = pb.src[i];
@@ -76,15 +76,16 @@ int kmap_presence_library_dev(const uint32_t *codes_dev, const uint16_t *inval_d
     unsigned long long *cnt_dev = nullptr;
     KMAP_TRY(kmap_scratch((void **)&cnt_dev, (size_t)n_mat * 8, st, KMAP_SLOT_B));
     KMAP_CHECK_HIP(hipMemsetAsync(cnt_dev, 0, (size_t)n_mat * 8, st));
-    KMAP_TRY(pwm_library_key_batches("presence_library", codes_dev, inval_dev, n, borders_dev, n_seq, n_mat, widths, weights, revcom, st,
-                                     [&](const LibKeys &keys) -> int {
+    KMAP_TRY(pwm_key_batches<ScoreKey>(
+        "presence_library", codes_dev, inval_dev, n, borders_dev, n_seq, n_mat, widths, weights, nullptr, revcom, nullptr, 0, st,
+        [&](const PwmBatch<false> &bt, const unsigned int *key, const int32_t *) -> int {
         PresBatch pb = {};
-        for (int j = 0; j < keys.n_mat; ++j) {
-            pb.src[j] = keys.src[j];
-            pb.tkey[j] = (uint32_t)thresholds[keys.src[j]] ^ 0x80000000u;
+        for (int j = 0; j < bt.n_mat; ++j) {
+            pb.src[j] = bt.src[j];
+            pb.tkey[j] = (uint32_t)thresholds[bt.src[j]] ^ 0x80000000u;
         }
-        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for(n_words, PR_WAVES), PR_BLOCKS / keys.n_mat));
-        presence_kernel<<<dim3(gx, (unsigned)keys.n_mat), PR_TPB, 0, st>>>(keys.key, n_seq, n_words, pb,
+        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for(n_words, PR_WAVES), PR_BLOCKS / bt.n_mat));
+        presence_kernel<<<dim3(gx, (unsigned)bt.n_mat), PR_TPB, 0, st>>>(key, n_seq, n_words, pb,
                                                                            (unsigned long long *)planes_dev, cnt_dev);
         KMAP_CHECK_HIP(hipGetLastError());
         return KMAP_OK;

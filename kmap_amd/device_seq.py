@@ -19,7 +19,7 @@ def _as_weights(W, who):
     return W
 
 
-LIBRARY_BATCH, LIBRARY_BATCH_CHUNKS = 8, 24    # csrc/pwm_library.hip: a batch is at most this many matrices and chunks of 4 columns
+LIBRARY_BATCH, LIBRARY_BATCH_CHUNKS = 8, 24    # csrc/pwm_batch.h: a batch is at most this many matrices and chunks of 4 columns
 LIBRARY_LDS_BINS, LIBRARY_MAX_BINS = 32768, 1 << 22      # ranges up to the first are counted in block-private bins; the second is the limit
 SITES_MAX_LEN = 1 << 20                        # csrc/pwm_sites.hip: the longest read library_sites makes histograms for
 SPACING_MAX_GAP = 511                          # csrc/pwm_spacing.hip: the largest gap library_spacing makes histograms for
@@ -31,6 +31,25 @@ def _as_threshold(t, who):
     if not -2 ** 31 <= int(t) < 2 ** 31:
         raise ValueError(f"{who}: threshold {t} does not fit int32")
     return int(t)
+
+
+def _pack_library(who, Ws, thresholds=None):
+    """the matrices of a library as the batched entry points take them (csrc/pwm_batch.h): (n_mat, widths int32[n_mat], weights
+    int32[n_mat, 4, 32] with zeros behind every width, thr int32[n_mat] or None without thresholds); ValueError under `who`"""
+    Ws = [_as_weights(W, who) for W in Ws]
+    n_mat, thr = len(Ws), None
+    if thresholds is not None:
+        thresholds = [_as_threshold(t, who) for t in thresholds]
+        if n_mat != len(thresholds):
+            raise ValueError(f"{who}: {n_mat} matrices, {len(thresholds)} thresholds")
+        thr = np.array(thresholds, np.int32).reshape(n_mat)
+    widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
+    for m, W in enumerate(Ws):
+        if not 4 <= W.shape[1] <= 31:
+            raise ValueError(f"{who}: matrix {m} has width {W.shape[1]}, outside 4..31")
+        widths[m] = W.shape[1]
+        weights[m, :, :W.shape[1]] = W
+    return n_mat, widths, weights, thr
 
 
 class DeviceSeq:
@@ -255,19 +274,13 @@ class DeviceSeq:
         reads per batch of matrices and without the per-read arrays (csrc/pwm_library.hip): returns
         (list of uint64[n_bins[m]], n_outside int64[n_mat]: scorable reads whose best score lies outside the range -- they are in no
         bin --, n_scored int64[n_mat]: reads with a valid window).  Needs no scan handle."""
-        Ws = [_as_weights(W, "library_histograms") for W in Ws]
+        n_mat, widths, weights, _ = _pack_library("library_histograms", Ws)
         los, n_bins = [int(x) for x in los], [int(x) for x in n_bins]
-        if not len(Ws) == len(los) == len(n_bins):
-            raise ValueError(f"library_histograms: {len(Ws)} matrices, {len(los)} range starts, {len(n_bins)} bin counts")
-        n_mat = len(Ws)
-        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
-        for m, (W, lo, nb) in enumerate(zip(Ws, los, n_bins)):
-            if not 4 <= W.shape[1] <= 31:
-                raise ValueError(f"library_histograms: matrix {m} has width {W.shape[1]}, outside 4..31")
+        if not n_mat == len(los) == len(n_bins):
+            raise ValueError(f"library_histograms: {n_mat} matrices, {len(los)} range starts, {len(n_bins)} bin counts")
+        for m, (lo, nb) in enumerate(zip(los, n_bins)):
             if not 0 <= nb <= LIBRARY_MAX_BINS or not -2 ** 31 <= lo < 2 ** 31:
                 raise ValueError(f"library_histograms: matrix {m}: {nb} bins from {lo}, at most 2^22 bins of int32 scores are supported")
-            widths[m] = W.shape[1]
-            weights[m, :, :W.shape[1]] = W
         lo_arr, nb_arr = np.array(los, np.int32).reshape(n_mat), np.array(n_bins, np.int64).reshape(n_mat)
         flat = np.zeros(int(nb_arr.sum()), np.uint64)
         outside, scored = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64)
@@ -293,23 +306,12 @@ class DeviceSeq:
         int64[n_mat][max_len + 1]: site reads of length L, n_sites int64[n_mat]: the sum of either, n_too_long int64[n_mat]: site
         reads longer than max_len, which are in neither histogram).  max_len None: the largest read length.  One pass over the
         original reads per batch of matrices, nothing per read leaves the device.  Needs no scan handle."""
-        Ws = [_as_weights(W, "library_sites") for W in Ws]
-        thresholds = [_as_threshold(t, "library_sites") for t in thresholds]
-        if len(Ws) != len(thresholds):
-            raise ValueError(f"library_sites: {len(Ws)} matrices, {len(thresholds)} thresholds")
-        n_mat = len(Ws)
-        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
-        for m, W in enumerate(Ws):
-            if not 4 <= W.shape[1] <= 31:
-                raise ValueError(f"library_sites: matrix {m} has width {W.shape[1]}, outside 4..31")
-            widths[m] = W.shape[1]
-            weights[m, :, :W.shape[1]] = W
+        n_mat, widths, weights, thr = _pack_library("library_sites", Ws, thresholds)
         if max_len is not None and (isinstance(max_len, bool) or int(max_len) != max_len or not 0 <= max_len <= SITES_MAX_LEN):
             raise ValueError(f"library_sites: max_len {max_len} outside 0 .. 2^20")
         max_len = self.max_read_len() if max_len is None else int(max_len)
         if max_len > SITES_MAX_LEN:
             raise ValueError(f"library_sites: the longest read has {max_len} bases, more than 2^20")
-        thr = np.array(thresholds, np.int32).reshape(n_mat)
         D, Hlen = np.zeros((n_mat, 2 * max_len + 1), np.uint64), np.zeros((n_mat, max_len + 1), np.uint64)
         sites, too_long = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64)
         check(_ffi.lib().kmap_readscore_sites_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,
@@ -323,18 +325,7 @@ class DeviceSeq:
         select_best=True) returns without n_hits, from library_sites' one pass over the original reads per batch of matrices:
         returns (list of int64[4, w_m]: C'[b][j] = selected windows whose oriented base j is b, n_selected int64[n_mat]: the site
         reads, n_minus int64[n_mat]: those on '-').  Nothing per read leaves the device.  Needs no scan handle."""
-        Ws = [_as_weights(W, "library_counts") for W in Ws]
-        thresholds = [_as_threshold(t, "library_counts") for t in thresholds]
-        if len(Ws) != len(thresholds):
-            raise ValueError(f"library_counts: {len(Ws)} matrices, {len(thresholds)} thresholds")
-        n_mat = len(Ws)
-        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
-        for m, W in enumerate(Ws):
-            if not 4 <= W.shape[1] <= 31:
-                raise ValueError(f"library_counts: matrix {m} has width {W.shape[1]}, outside 4..31")
-            widths[m] = W.shape[1]
-            weights[m, :, :W.shape[1]] = W
-        thr = np.array(thresholds, np.int32).reshape(n_mat)
+        n_mat, widths, weights, thr = _pack_library("library_counts", Ws, thresholds)
         counts = np.zeros((n_mat, 4, 32), np.uint64)
         n_sel, n_minus = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64)
         check(_ffi.lib().kmap_readscore_counts_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,
@@ -354,25 +345,15 @@ class DeviceSeq:
         most max_gap, n_primary, n_pair int64[n_mat]: primary reads with a secondary site, n_far int64[n_mat]: those with
         g > max_gap, which are in neither histogram).  One pass over the original reads per batch of matrices, nothing per read
         leaves the device.  Needs no scan handle."""
-        Ws = [_as_weights(W, "library_spacing") for W in Ws]
-        thresholds = [_as_threshold(t, "library_spacing") for t in thresholds]
+        n_mat, widths, weights, thr = _pack_library("library_spacing", Ws, thresholds)
         prim_threshold = _as_threshold(prim_threshold, "library_spacing")
-        if len(Ws) != len(thresholds):
-            raise ValueError(f"library_spacing: {len(Ws)} matrices, {len(thresholds)} thresholds")
         if isinstance(prim_width, bool) or int(prim_width) != prim_width or not 4 <= prim_width <= 31:
             raise ValueError(f"library_spacing: the primary matrix has width {prim_width}, outside 4..31")
         if isinstance(max_gap, bool) or int(max_gap) != max_gap or not 0 <= max_gap <= SPACING_MAX_GAP:
             raise ValueError(f"library_spacing: max_gap {max_gap} outside 0 .. {SPACING_MAX_GAP}")
         if not isinstance(primary, ReadScores) or primary.n_seq != self.n_seq:
             raise ValueError(f"library_spacing: the primary must be the ReadScores of these {self.n_seq} reads")
-        n_mat, G = len(Ws), int(max_gap)
-        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
-        for m, W in enumerate(Ws):
-            if not 4 <= W.shape[1] <= 31:
-                raise ValueError(f"library_spacing: matrix {m} has width {W.shape[1]}, outside 4..31")
-            widths[m] = W.shape[1]
-            weights[m, :, :W.shape[1]] = W
-        thr = np.array(thresholds, np.int32).reshape(n_mat)
+        G = int(max_gap)
         S, R = np.zeros((n_mat, 4, G + 1), np.uint64), np.zeros((n_mat, G + 2, G + 2), np.uint64)
         pair, far, n_primary = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64), _ffi.i64(0)
         check(_ffi.lib().kmap_readscore_spacing_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq,
@@ -387,18 +368,7 @@ class DeviceSeq:
         (csrc/pwm_presence.hip).  Returns a PresencePlanes: one bit per (matrix, read) in HBM and n_present
         int64[n_mat].  One pass over the original reads per batch of matrices, nothing per read leaves the device.  Needs no scan
         handle."""
-        Ws = [_as_weights(W, "library_presence") for W in Ws]
-        thresholds = [_as_threshold(t, "library_presence") for t in thresholds]
-        if len(Ws) != len(thresholds):
-            raise ValueError(f"library_presence: {len(Ws)} matrices, {len(thresholds)} thresholds")
-        n_mat = len(Ws)
-        widths, weights = np.zeros(n_mat, np.int32), np.zeros((n_mat, 4, 32), np.int32)
-        for m, W in enumerate(Ws):
-            if not 4 <= W.shape[1] <= 31:
-                raise ValueError(f"library_presence: matrix {m} has width {W.shape[1]}, outside 4..31")
-            widths[m] = W.shape[1]
-            weights[m, :, :W.shape[1]] = W
-        thr = np.array(thresholds, np.int32).reshape(n_mat)
+        n_mat, widths, weights, thr = _pack_library("library_presence", Ws, thresholds)
         out = PresencePlanes(n_mat, self.n_seq)
         try:
             check(_ffi.lib().kmap_presence_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,

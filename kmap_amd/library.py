@@ -7,6 +7,7 @@ motif into pwm.py's integer weights and threshold, and has csrc/pwm_library.hip 
 in one pass each, straight to the histograms of the best scores.  Behind the kernel everything is evaluate.py's exact integer
 arithmetic on two histograms per motif; added here are the one-sided p of the Mann-Whitney z, Benjamini-Hochberg q-values over the
 library and the ranking.  Host code is parsing, that arithmetic and the file formats; the scoring has no CPU path."""
+import contextlib
 import math
 import re
 from pathlib import Path
@@ -138,6 +139,60 @@ def read_motif_library(path, nsites_default=20):
     return [LibraryMotif(p.stem, "", path, read_count_matrix(str(path)))]
 
 
+def load_library(who, library_files, nsites_default, pseudocount, p_value, t_fixed=None, veto=None):
+    """What the library verbs score: every motif of library_files (read_motif_library, in file order) as pwm.py's integer weights
+    and threshold.  Returns (motifs, skipped, Ws, plans): the motifs kept, those left out with `skip` set (a width outside 4..31,
+    or veto(W, t, lo, hi) gave the reason), and per motif kept W and plan = pwm_threshold(W, p_value)'s (t, lo, hi) -- with t_fixed
+    in t's place when one is given.  ValueError: a file that cannot be read, `{source}: motif {name}: ...` for a matrix without
+    weights or threshold, and under `who` a library none of whose motifs is kept."""
+    motifs, skipped, Ws, plans = [], [], [], []
+    for f in library_files:
+        for m in read_motif_library(f, nsites_default):
+            if m.skip is None:
+                try:
+                    W = pwm_weights(m.counts, pseudocount)
+                    t, lo, hi = pwm_threshold(W, p_value)
+                except ValueError as exc:
+                    raise ValueError(f"{m.source}: motif {m.name}: {exc}") from None
+                if veto is not None:
+                    m.skip = veto(W, t, lo, hi)
+            if m.skip is None:
+                motifs.append(m)
+                Ws.append(W)
+                plans.append((t if t_fixed is None else t_fixed, lo, hi))
+            else:
+                skipped.append(m)
+    if not motifs:
+        raise ValueError(f"{who}: none of the {len(skipped)} motifs of the library can be scored "
+                         f"(the first: {skipped[0].name}: {skipped[0].skip})")
+    return motifs, skipped, Ws, plans
+
+
+@contextlib.contextmanager
+def open_read_sets(seq_path, border_path, control_fasta_file=None):
+    """(fg_seq, ctl_seq): the encoded reads of a result directory and, with a control FASTA, the control reads (else None) as
+    DeviceSeq, the foreground opened first; both are closed on the way out"""
+    from .kmer_count import encode_fasta, load_array_pickle
+    from .motif_discovery import DeviceSeq
+    fg_seq = DeviceSeq(load_array_pickle(seq_path), load_array_pickle(border_path))
+    ctl_seq = None
+    try:
+        if control_fasta_file is not None:
+            ctl_seq = DeviceSeq(*encode_fasta(str(control_fasta_file)))
+        yield fg_seq, ctl_seq
+    finally:
+        for h in (ctl_seq, fg_seq):
+            if h is not None:
+                h.close()
+
+
+def write_skipped(out, skipped):
+    """skipped.csv in the directory `out`: the motifs that were not scored and why"""
+    with open(out / SKIPPED_FILE, "w") as fh:
+        fh.write(SKIPPED_HEADER)
+        fh.write("".join(f"{m.name},{m.altname},{m.source},{_field(m.skip)}\n" for m in skipped))
+
+
 def bh_qvalues(p):
     """Benjamini-Hochberg q-values of the p-values (nan counts as 1): the step-up procedure, q of the i-th smallest of n = the
     minimum over j >= i of p_(j) n / j, at most 1.  The sort is stable (ties keep the input order; they get the same q)."""
@@ -183,7 +238,7 @@ def _rank_motif_library(res_dir, control_fasta_file, library_files, p_value=1e-4
     a file is written; motifs that cannot be scored (width outside 4..31, more than 2^22 different scores) are listed in skipped.csv.
     Under a torch.distributed launch rank 0 works alone.  Returns one dict per evaluated motif in rank order: evaluate_histograms'
     fields plus motif, rank, Hf, Hc, lo, fg_unscorable, control_unscorable, log10_p, q_bh."""
-    from .kmer_count import encode_fasta, load_array_pickle, load_config, rank0_only, result_paths
+    from .kmer_count import load_config, rank0_only, result_paths
     if not rank0_only():
         return None
     res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
@@ -198,44 +253,21 @@ def _rank_motif_library(res_dir, control_fasta_file, library_files, p_value=1e-4
         raise ValueError(f"top_hist {top_hist} < 0")
     _, revcom = load_config(cfg_path, revcom_mode)
 
-    motifs, skipped, plans = [], [], []                      # plans: (W, t, lo, hi) per motif kept
-    for f in library_files:
-        for m in read_motif_library(f, nsites_default):
-            if m.skip is None:
-                try:
-                    W = pwm_weights(m.counts, pseudocount)
-                    t, lo, hi = pwm_threshold(W, p_value)
-                except ValueError as exc:
-                    raise ValueError(f"{m.source}: motif {m.name}: {exc}") from None
-                if hi - lo + 1 > MAX_BINS:
-                    m.skip = f"scores from {lo} to {hi}: more than 2^22 different scores"
-            if m.skip is None:
-                motifs.append(m)
-                plans.append((W, t, lo, hi))
-            else:
-                skipped.append(m)
-    if not motifs:
-        raise ValueError(f"rank_motif_library: none of the {len(skipped)} motifs of the library can be scored "
-                         f"(the first: {skipped[0].name}: {skipped[0].skip})")
+    motifs, skipped, Ws, plans = load_library(
+        "rank_motif_library", library_files, nsites_default, pseudocount, p_value,
+        veto=lambda W, t, lo, hi: f"scores from {lo} to {hi}: more than 2^22 different scores" if hi - lo + 1 > MAX_BINS else None)
 
-    from .motif_discovery import DeviceSeq
-    Ws, los, nbs = [p[0] for p in plans], [p[2] for p in plans], [p[3] - p[2] + 1 for p in plans]
-    fg_seq = DeviceSeq(load_array_pickle(seq_path), load_array_pickle(border_path))
-    ctl_seq, per_set = None, []
-    try:
-        ctl_seq = DeviceSeq(*encode_fasta(str(control_fasta_file)))
-        for ds in (fg_seq, ctl_seq):
+    los, nbs = [p[1] for p in plans], [p[2] - p[1] + 1 for p in plans]
+    per_set = []
+    with open_read_sets(seq_path, border_path, control_fasta_file) as read_sets:
+        for ds in read_sets:
             hists, outside, scored = ds.library_histograms(Ws, los, nbs, revcom)
             if np.any(np.asarray(outside) != 0):
                 raise ValueError(f"rank_motif_library: reads score outside the score range of motif {motifs[int(np.nonzero(outside)[0][0])].name}")
             per_set.append((hists, [ds.n_seq - int(s) for s in scored]))
-    finally:
-        for h in (ctl_seq, fg_seq):
-            if h is not None:
-                h.close()
 
     results = []
-    for i, (m, (W, t, lo, hi)) in enumerate(zip(motifs, plans)):
+    for i, (m, (t, lo, hi)) in enumerate(zip(motifs, plans)):
         Hf, Hc = per_set[0][0][i], per_set[1][0][i]
         st = evaluate_histograms(Hf, Hc, lo, t, min_reads)
         st.update(motif=m, Hf=Hf, Hc=Hc, lo=lo, fg_unscorable=per_set[0][1][i], control_unscorable=per_set[1][1][i],
@@ -252,9 +284,7 @@ def _rank_motif_library(res_dir, control_fasta_file, library_files, p_value=1e-4
         for rank, st in enumerate(results):
             st["rank"] = rank
             fh.write(rank_line(rank, st["motif"], pseudocount, revcom, st))
-    with open(out / SKIPPED_FILE, "w") as fh:
-        fh.write(SKIPPED_HEADER)
-        fh.write("".join(f"{m.name},{m.altname},{m.source},{_field(m.skip)}\n" for m in skipped))
+    write_skipped(out, skipped)
     for st in results[:int(top_hist)]:
         write_score_hist(out / HIST_FILE.format(rank=st["rank"], name=_file_name(st["motif"].name)), st["Hf"], st["Hc"], st["lo"])
     for st in results[:10]:

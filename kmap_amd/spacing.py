@@ -15,7 +15,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .library import SKIPPED_HEADER, _field, _file_name, bh_qvalues, rank_order, read_motif_library
+from .library import _field, _file_name, bh_qvalues, load_library, open_read_sets, rank_order, read_motif_library, write_skipped
 from .pwm import SCORE_UNIT, min_score_threshold, pwm_consensus, pwm_threshold, pwm_weights
 
 OUTPUT_DIR, RANK_FILE, SKIPPED_FILE, HIST_FILE = "motif_spacing", "spacing_rank.csv", "skipped.csv", "spacing_{rank}_{name}.csv"
@@ -165,7 +165,7 @@ def _motif_spacing(res_dir, primary_file, library_files, primary_name=None, p_va
     or a file is written; motifs whose width lies outside 4..31 are listed in skipped.csv.  Under a torch.distributed launch rank
     0 works alone.  Returns one dict per motif in rank order: best_bin's fields plus motif, rank, threshold, S, R, n_primary,
     n_pairs, n_far and q_bh."""
-    from .kmer_count import load_array_pickle, load_config, rank0_only, result_paths
+    from .kmer_count import load_config, rank0_only, result_paths
     if not rank0_only():
         return None
     res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
@@ -190,34 +190,15 @@ def _motif_spacing(res_dir, primary_file, library_files, primary_name=None, p_va
         tP = pwm_threshold(W_P, p_value)[0] if tP_fixed is None else tP_fixed
     except ValueError as exc:
         raise ValueError(f"{primary.source}: motif {primary.name}: {exc}") from None
-    motifs, skipped, Ws, ts = [], [], [], []
-    for f in library_files:
-        for m in read_motif_library(f, nsites_default):
-            if m.skip is not None:
-                skipped.append(m)
-                continue
-            try:
-                W = pwm_weights(m.counts, pseudocount)
-                t = pwm_threshold(W, p_value)[0]
-            except ValueError as exc:
-                raise ValueError(f"{m.source}: motif {m.name}: {exc}") from None
-            motifs.append(m)
-            Ws.append(W)
-            ts.append(t if t_fixed is None else t_fixed)
-    if not motifs:
-        raise ValueError(f"motif_spacing: none of the {len(skipped)} motifs of the library can be scored "
-                         f"(the first: {skipped[0].name}: {skipped[0].skip})")
+    motifs, skipped, Ws, plans = load_library("motif_spacing", library_files, nsites_default, pseudocount, p_value, t_fixed)
+    ts = [p[0] for p in plans]
 
-    from .motif_discovery import DeviceSeq
-    seq = DeviceSeq(load_array_pickle(seq_path), load_array_pickle(border_path))
-    scores = None
-    try:
+    with open_read_sets(seq_path, border_path) as (seq, _):
         scores = seq.read_scores(W_P, revcom)
-        S, R, n_primary, n_pair, n_far = seq.library_spacing(scores, W_P.shape[1], tP, Ws, ts, revcom, int(max_gap))
-    finally:
-        if scores is not None:
+        try:
+            S, R, n_primary, n_pair, n_far = seq.library_spacing(scores, W_P.shape[1], tP, Ws, ts, revcom, int(max_gap))
+        finally:
             scores.close()
-        seq.close()
 
     results = []
     for i, (m, t) in enumerate(zip(motifs, ts)):
@@ -239,9 +220,7 @@ def _motif_spacing(res_dir, primary_file, library_files, primary_name=None, p_va
         for rank, st in enumerate(results):
             st["rank"] = rank
             fh.write(rank_line(rank, st["motif"], st["threshold"], st))
-    with open(out / SKIPPED_FILE, "w") as fh:
-        fh.write(SKIPPED_HEADER)
-        fh.write("".join(f"{m.name},{m.altname},{m.source},{_field(m.skip)}\n" for m in skipped))
+    write_skipped(out, skipped)
     for st in results[:int(top_hist)]:
         write_gap_histogram(out / HIST_FILE.format(rank=st["rank"], name=_file_name(st["motif"].name)), st["S"], st["E"])
     print(f"primary {primary.name}{' ' + primary.altname if primary.altname else ''}: at {tP / SCORE_UNIT:.2f} bits "

@@ -335,8 +335,9 @@ def test_symbol_registered_and_constants():
     assert res is _ffi.i32 and len(args) == 16
     assert not name.startswith("kmap_pwm_")
     src = (ROOT / "kmap_amd" / "csrc" / "pwm_sites.hip").read_text()
-    assert int(re.search(r"constexpr int ST_MAX_MAT = (\d+);", src).group(1)) == device_seq.LIBRARY_BATCH
-    assert int(re.search(r"constexpr int ST_MAX_CHUNKS = (\d+);", src).group(1)) == device_seq.LIBRARY_BATCH_CHUNKS
+    batch = (ROOT / "kmap_amd" / "csrc" / "pwm_batch.h").read_text()
+    assert int(re.search(r"constexpr int PB_MAX_MAT = (\d+);", batch).group(1)) == device_seq.LIBRARY_BATCH
+    assert int(re.search(r"constexpr int PB_MAX_CHUNKS = (\d+);", batch).group(1)) == device_seq.LIBRARY_BATCH_CHUNKS
     assert 1 << int(re.search(r"constexpr int64_t ST_MAX_LEN = 1ll << (\d+);", src).group(1)) == device_seq.SITES_MAX_LEN
 
 

@@ -359,9 +359,10 @@ def test_symbols_registered_and_constants():
     assert int(re.search(r"constexpr int BP_MAX_ROWS = (\d+);", src).group(1)) == device_seq.BIT_PAIRS_MAX_ROWS == cooccurrence.MAX_MOTIFS
     assert device_seq.BIT_PAIRS_MIN_SLICE % device_seq.BIT_PAIRS_K == 0
     src = (ROOT / "kmap_amd" / "csrc" / "pwm_presence.hip").read_text()
-    assert int(re.search(r"constexpr int PR_MAX_MAT = (\d+);", src).group(1)) == device_seq.LIBRARY_BATCH
-    # the scoring kernel exists once: the presence planes go through pwm_library.hip's batch pass
-    assert "readscore_multi_kernel" not in re.sub(r"//.*", "", src) and "pwm_library_key_batches(" in src
+    batch = (ROOT / "kmap_amd" / "csrc" / "pwm_batch.h").read_text()
+    assert int(re.search(r"constexpr int PB_MAX_MAT = (\d+);", batch).group(1)) == device_seq.LIBRARY_BATCH
+    # the scoring kernel exists once, in the header: the presence planes go through its batch pass with the score key
+    assert "__global__" in batch and "pwm_batch_kernel" not in re.sub(r"//.*", "", src) and "pwm_key_batches<ScoreKey>(" in src
 
 
 def test_library_presence_checks_come_before_the_library(monkeypatch):

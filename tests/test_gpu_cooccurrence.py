@@ -11,6 +11,7 @@ import pytest
 from tests import _cooccurrence_model as CM
 from tests import _readscore_model as M
 from tests import _sites_model as S
+from tests._batch_model import batches
 from tests._refine_model import asym_matrix, make_reads, window_scores
 
 pytestmark = pytest.mark.gpu
@@ -21,19 +22,6 @@ LIB = ROOT / "tests" / "golden" / "library"
 # eleven random matrices and an all-zero one.  By width the eight narrow ones fill a batch (the 8-matrix limit cuts), three of the
 # four 31-column ones fill the next (the 24-chunk limit cuts), the fourth is alone.
 WIDTHS = (4, 9, 16, 31, 31, 31, 31, 5, 6, 7, 12)
-
-
-def batches(widths):
-    """the batches of csrc/pwm_library.hip for these widths: [(number of matrices, why it closed)]"""
-    from kmap_amd.device_seq import LIBRARY_BATCH as B, LIBRARY_BATCH_CHUNKS as CH
-    out, n, chunks = [], 0, 0
-    for w in sorted(widths):
-        nch = (w + 3) // 4
-        if n == B or chunks + nch > CH:
-            out.append((n, "matrices" if n == B else "chunks"))
-            n, chunks = 0, 0
-        n, chunks = n + 1, chunks + nch
-    return out + [(n, "end")]
 
 
 @pytest.fixture(scope="module")

@@ -11,6 +11,7 @@ import pytest
 
 from tests import _readscore_model as M
 from tests import _spacing_model as S
+from tests._batch_model import batches
 from tests._refine_model import asym_matrix, make_reads, window_scores
 
 pytestmark = pytest.mark.gpu
@@ -241,19 +242,6 @@ def test_gap_exactly_max_gap_and_one_more(gap_reads, G):
 
 
 # ---- 3. batching ----------------------------------------------------------------------------------------------------------------------
-def batches(widths):
-    """the batches of csrc/pwm_spacing.hip for these widths: [(number of matrices, why it closed)]"""
-    from kmap_amd.device_seq import LIBRARY_BATCH as B, LIBRARY_BATCH_CHUNKS as CH
-    out, n, chunks = [], 0, 0
-    for w in sorted(widths):
-        nch = (w + 3) // 4
-        if n == B or chunks + nch > CH:
-            out.append((n, "matrices" if n == B else "chunks"))
-            n, chunks = 0, 0
-        n, chunks = n + 1, chunks + nch
-    return out + [(n, "end")]
-
-
 def test_batches_permutation_and_prefixes(geometry):
     from kmap_amd.pwm import pwm_threshold
     ds, seq, borders, _, _, prim, _ = geometry

@@ -346,8 +346,9 @@ def test_symbol_registered_and_batch_constants():
     res, args = _ffi._SIGS[name]
     assert res is _ffi.i32 and len(args) == 15
     src = (ROOT / "kmap_amd" / "csrc" / "pwm_library.hip").read_text()
-    assert int(re.search(r"constexpr int LB_MAX_MAT = (\d+);", src).group(1)) == device_seq.LIBRARY_BATCH
-    assert int(re.search(r"constexpr int LB_MAX_CHUNKS = (\d+);", src).group(1)) == device_seq.LIBRARY_BATCH_CHUNKS
+    batch = (ROOT / "kmap_amd" / "csrc" / "pwm_batch.h").read_text()
+    assert int(re.search(r"constexpr int PB_MAX_MAT = (\d+);", batch).group(1)) == device_seq.LIBRARY_BATCH
+    assert int(re.search(r"constexpr int PB_MAX_CHUNKS = (\d+);", batch).group(1)) == device_seq.LIBRARY_BATCH_CHUNKS
     assert int(re.search(r"constexpr int64_t LB_HIST_LDS_BINS = (\d+);", src).group(1)) == device_seq.LIBRARY_LDS_BINS
     assert device_seq.LIBRARY_BATCH_CHUNKS >= 8               # the widest matrix has 8 chunks of 4 columns: a batch is never empty
 

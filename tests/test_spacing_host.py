@@ -407,8 +407,9 @@ def test_symbol_registered_and_constants():
     assert declared.count(",") + 1 == 22
     assert not name.startswith("kmap_pwm_")
     src = (ROOT / "kmap_amd" / "csrc" / "pwm_spacing.hip").read_text()
-    assert int(re.search(r"constexpr int SP_MAX_MAT = (\d+);", src).group(1)) == device_seq.LIBRARY_BATCH
-    assert int(re.search(r"constexpr int SP_MAX_CHUNKS = (\d+);", src).group(1)) == device_seq.LIBRARY_BATCH_CHUNKS
+    batch = (ROOT / "kmap_amd" / "csrc" / "pwm_batch.h").read_text()
+    assert int(re.search(r"constexpr int PB_MAX_MAT = (\d+);", batch).group(1)) == device_seq.LIBRARY_BATCH
+    assert int(re.search(r"constexpr int PB_MAX_CHUNKS = (\d+);", batch).group(1)) == device_seq.LIBRARY_BATCH_CHUNKS
     assert int(re.search(r"constexpr int SP_MAX_GAP = (\d+);", src).group(1)) == device_seq.SPACING_MAX_GAP == spacing.MAX_GAP == 511
 
 
