@@ -504,7 +504,10 @@ int kmap_gather_dev(const void *src_dev, int elem_bytes, const int64_t *idx, int
  * anything else -> 255, one 255 separator after every record; borders [start, end) with end = index of the separator; text
  * before the first header is ignored.  Two-call pattern: open reports the sizes, read fills the caller's arrays.  A plain file
  * is mapped and cut behind newlines into ranges that host threads walk (KMAP_IO_THREADS, default <= 16): open counts them, read
- * encodes each range straight into seq_out / borders_out; a gzip stream is encoded by one thread while it is inflated. */
+ * encodes each range straight into seq_out / borders_out; a gzip stream is encoded by one thread while it is inflated.
+ * KMAP_IO_THREADS (read on every call; unset: min(16, cores)) caps the host threads of every native I/O entry: this reader, the
+ * occurrence-CSV / BED parsers and the BED writer below, kmap_write_occurrence_csv[_u8], kmap_write_f2_tsv_line, and the
+ * conversion pool of kmap_counts_fetch / kmap_counts_fetch_stream.  All of them share csrc/host_pool.h. */
 typedef struct kmap_fasta kmap_fasta;
 int kmap_fasta_open(const char *path, kmap_fasta **f, int64_t *n_bytes, int64_t *n_seq);
 int kmap_fasta_read(kmap_fasta *f, uint8_t *seq_out, int64_t *borders_out);

@@ -6,7 +6,6 @@
 
 #include <algorithm>
 #include <mutex>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -29,7 +28,7 @@ int kmap_counts_fetch(kmap_counts *c, void *uniq_out, void *cnt_out) {
         KMAP_REQUIRE(tmp, "counts_fetch: host malloc");
         hipError_t e = hipMemcpy(tmp, c->cnt, n * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess)   // widen uint32 -> int64 on several host threads (10^9 entries at k = 16)
-            kmap_convert_pool<uint32_t, int64_t>((int64_t *)cnt_out, tmp, n, std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
+            kmap_convert_pool<uint32_t, int64_t>((int64_t *)cnt_out, tmp, n, kmap_io_threads());
         free(tmp);
         KMAP_CHECK_HIP(e);
     }
@@ -79,7 +78,7 @@ int staged_fetch(DST *dst, const SRC *src_dev, size_t n, hipStream_t st) {
     }
     const size_t chunk = STAGE_BYTES / sizeof(SRC);               // elements per chunk
     SRC *stage[2] = {(SRC *)sp.buf[0], (SRC *)sp.buf[1]};
-    const unsigned nt = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    const unsigned nt = kmap_io_threads();
     hipError_t err = hipSuccess;
     size_t off = 0;
     int b = 0;
@@ -104,21 +103,6 @@ int staged_fetch(DST *dst, const SRC *src_dev, size_t n, hipStream_t st) {
 __global__ __launch_bounds__(256) void widen_counts_kernel(const uint32_t *__restrict__ in, int64_t n, int64_t *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = (int64_t)in[i];
-}
-
-// write() in full (short writes, EINTR); false + errno on failure
-static bool pwrite_all(int fd, const char *buf, size_t len, int64_t off) {
-    while (len) {
-        const ssize_t w = pwrite(fd, buf, len, (off_t)off);
-        if (w < 0) {
-            if (errno == EINTR) continue;
-            return false;
-        }
-        buf += w;
-        off += w;
-        len -= (size_t)w;
-    }
-    return true;
 }
 
 // `n` elements of a device array -> file bytes at `file_off`, in the file's dtype DST: chunk i + 1 crosses PCIe into one pinned
@@ -155,7 +139,7 @@ int staged_write(int fd, int64_t file_off, const SRC *src_dev, size_t n, hipStre
         if (err != hipSuccess) break;
         const size_t next_off = off + len, next_len = next_off < n ? std::min(chunk, n - next_off) : 0;
         if (next_len) err = issue(b ^ 1, next_off, next_len);
-        if (!pwrite_all(fd, (const char *)sp.buf[b], len * sizeof(DST), file_off + (int64_t)(off * sizeof(DST)))) {
+        if (!kmap_pwrite_all(fd, (const char *)sp.buf[b], len * sizeof(DST), file_off + (int64_t)(off * sizeof(DST)))) {
             const int en = errno;
             (void)hipStreamSynchronize(st);
             kmap_set_error("counts_write: pwrite failed: %s", strerror(en));

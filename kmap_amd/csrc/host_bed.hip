@@ -9,109 +9,58 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <memory>
 #include <new>
 #include <string>
 #include <string_view>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
 #include "common.h"
+#include "host_pool.h"
 
 namespace {
-unsigned io_threads() {
-    const char *v = getenv("KMAP_IO_THREADS");
-    const int cap = v ? std::max(1, atoi(v)) : 16;
-    return (unsigned)std::min<int>((int)std::max(1u, std::thread::hardware_concurrency()), cap);
-}
-// fn(t) for t in [0, n) on up to `nt` threads (the calling thread takes its share; threads that cannot be started are not missed)
-template <typename F>
-void run_parallel(size_t n, unsigned nt, F fn) {
-    std::atomic<size_t> next{0};
-    auto worker = [&]() {
-        for (;;) {
-            const size_t t = next.fetch_add(1);
-            if (t >= n) return;
-            fn(t);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (unsigned i = 1; i < nt && i < n; ++i) pool.emplace_back(worker);
-    } catch (...) {
-    }
-    worker();
-    for (auto &th : pool) th.join();
-}
-
 // the whole file, memory-mapped (or read, for what cannot be mapped)
 struct Text {
     const char *p = nullptr;
     size_t n = 0;
-    void *map = nullptr;
+    KmapMappedFile in;
     std::vector<char> buf;
-    ~Text() {
-        if (map) munmap(map, n);
-    }
 };
 int load_text(const char *path, Text &t, const char *who) {
-    const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) {
+    if (!t.in.open(path)) {
         kmap_set_error("%s: cannot open %s: %s", who, path, strerror(errno));
         return KMAP_E_IO;
     }
-    struct stat sb;
-    if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {
-        void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
-        if (m != MAP_FAILED) {
-            t.map = m;
-            t.p = (const char *)m;
-            t.n = (size_t)sb.st_size;
-            close(fd);
-            return KMAP_OK;
-        }
+    if (t.in.map()) {
+        (void)t.in.file.close();
+        t.p = t.in.p;
+        t.n = t.in.n;
+        return KMAP_OK;
     }
     char chunk[1 << 16];
     for (;;) {
-        const ssize_t r = read(fd, chunk, sizeof chunk);
+        const ssize_t r = read(t.in.file.fd, chunk, sizeof chunk);
         if (r < 0) {
             kmap_set_error("%s: read error on %s: %s", who, path, strerror(errno));
-            close(fd);
             return KMAP_E_IO;
         }
         if (r == 0) break;
         t.buf.insert(t.buf.end(), chunk, chunk + r);
     }
-    close(fd);
+    (void)t.in.file.close();
     t.p = t.buf.data();
     t.n = t.buf.size();
     return KMAP_OK;
 }
 
-// [lo, n) cut behind newlines into ranges of >= KMAP_TEXT_MIN_CHUNK bytes, about 4 per thread
-std::vector<size_t> cut_lines(const char *p, size_t lo, size_t n, unsigned threads) {
+// [lo, n) cut behind newlines into ranges of >= KMAP_TEXT_MIN_CHUNK bytes (default 1 MiB), about 4 per thread
+std::vector<size_t> cut_text(const Text &t, size_t lo, unsigned threads) {
     const char *mc = getenv("KMAP_TEXT_MIN_CHUNK");
-    const size_t min_chunk = mc ? (size_t)std::max(1ll, atoll(mc)) : ((size_t)1 << 20);
-    const size_t len = n - lo;
-    const size_t want = std::max<size_t>(1, std::min<size_t>((size_t)threads * 4, len / min_chunk));
-    std::vector<size_t> cut{lo};
-    for (size_t t = 1; t < want; ++t) {
-        const size_t from = std::max(cut.back(), lo + (len / want) * t);
-        if (from >= n) break;
-        const char *nl = (const char *)memchr(p + from, '\n', n - from);
-        if (!nl || (size_t)(nl - p) + 1 >= n) break;
-        const size_t at = (size_t)(nl - p) + 1;
-        if (at > cut.back()) cut.push_back(at);
-    }
-    cut.push_back(n);
-    return cut;
+    return kmap_cut_lines(t.p, lo, t.n, threads, mc ? (size_t)std::max(1ll, atoll(mc)) : ((size_t)1 << 20));
 }
 // fn(begin, end, byte offset) for every line of [lo, hi) without its '\n' and one trailing '\r'; empty lines are skipped (pandas
 // skips them).  fn returns false to stop.
@@ -187,15 +136,15 @@ static int occ_open_impl(const char *path, kmap_occ **out, int64_t *n_rows, int 
     size_t hdr_end = nl ? (size_t)(nl - t.p) : t.n;
     KMAP_REQUIRE(t.n > 0 && hdr_end > 0, "occurrence file %s: no header line", path);
     std::unique_ptr<kmap_occ> o(new kmap_occ());
-    o->threads = io_threads();
+    o->threads = kmap_io_threads();
     const int fields = 1 + (int)std::count(t.p, t.p + hdr_end, ';');
     KMAP_REQUIRE(fields >= 2, "occurrence file %s: the header has %d field(s), `seq_ind;...;seq_len` has at least 2", path, fields);
     const int nc = fields - 2;
     o->n_cols = nc;
     const size_t body = nl ? hdr_end + 1 : t.n;
-    const std::vector<size_t> cut = cut_lines(t.p, body, t.n, o->threads);
+    const std::vector<size_t> cut = cut_text(t, body, o->threads);
     o->parts.resize(cut.size() - 1);
-    run_parallel(o->parts.size(), o->threads, [&](size_t i) {
+    kmap_parallel_for(o->parts.size(), o->threads, [&](size_t i) {
         kmap_occ::Part &pt = o->parts[i];
         pt.hits.resize((size_t)nc);
         pt.pos.resize((size_t)nc);
@@ -283,7 +232,7 @@ extern "C" int kmap_occ_read(const kmap_occ *o, int64_t *seq_ind, int64_t *seq_l
         row0[i + 1] = row0[i] + (int64_t)o->parts[i].seq_ind.size();
         for (size_t c = 0; c < nc; ++c) pos0[(i + 1) * nc + c] = pos0[i * nc + c] + (int64_t)o->parts[i].pos[c].size();
     }
-    run_parallel(np, o->threads, [&](size_t i) {
+    kmap_parallel_for(np, o->threads, [&](size_t i) {
         const kmap_occ::Part &pt = o->parts[i];
         const size_t n = pt.seq_ind.size();
         if (n) {
@@ -328,7 +277,7 @@ static int bed_open_impl(const char *path, kmap_bed **out, int64_t *n_rows, int 
     Text t;
     KMAP_TRY(load_text(path, t, "bed_open"));
     std::unique_ptr<kmap_bed> bed(new kmap_bed());
-    bed->threads = io_threads();
+    bed->threads = kmap_io_threads();
     int nf = 0;                                                   // fields of the first line decide the width
     for_lines(t.p, 0, t.n, [&](const char *b, const char *e, size_t) {
         nf = 1 + (int)std::count(b, e, '\t');
@@ -343,9 +292,9 @@ static int bed_open_impl(const char *path, kmap_bed **out, int64_t *n_rows, int 
         std::vector<std::string_view> chrom_names, strand_names;
         std::string err;
     };
-    const std::vector<size_t> cut = cut_lines(t.p, 0, t.n, bed->threads);
+    const std::vector<size_t> cut = cut_text(t, 0, bed->threads);
     std::vector<Part> parts(cut.size() - 1);
-    run_parallel(parts.size(), bed->threads, [&](size_t i) {
+    kmap_parallel_for(parts.size(), bed->threads, [&](size_t i) {
         Part &pt = parts[i];
         auto intern = [](std::unordered_map<std::string_view, uint32_t> &ids, std::vector<std::string_view> &names, std::string_view s) {
             auto it = ids.find(s);
@@ -430,7 +379,7 @@ static int bed_open_impl(const char *path, kmap_bed **out, int64_t *n_rows, int 
     bed->start.resize(n);
     bed->chrom_rank.resize(n);
     bed->strand.resize(n);
-    run_parallel(parts.size(), bed->threads, [&](size_t i) {
+    kmap_parallel_for(parts.size(), bed->threads, [&](size_t i) {
         const Part &pt = parts[i];
         const size_t m = pt.start.size();
         if (m) memcpy(bed->start.data() + row0[i], pt.start.data(), m * 8);
@@ -478,24 +427,6 @@ extern "C" int kmap_bed_chrom(const kmap_bed *b, int rank, char *buf, int cap) {
 }
 
 // ---- the per-consensus output: "chrom\tstart\tend\tname\tscore\tstrand" like pandas to_csv(sep='\t', index=False) --------------
-namespace {
-inline char *put_i64(char *p, int64_t v) {
-    uint64_t u = (uint64_t)v;
-    if (v < 0) {
-        *p++ = '-';
-        u = 0ull - u;
-    }
-    char tmp[24];
-    int n = 0;
-    do {
-        tmp[n++] = (char)('0' + u % 10);
-        u /= 10;
-    } while (u);
-    while (n) *p++ = tmp[--n];
-    return p;
-}
-}  // namespace
-
 static int bed_write_impl(const kmap_bed *b, const char *path, int cons_index, int64_t n, const int64_t *row, const int64_t *start,
                           const int64_t *end, int64_t *bytes_written) {
     KMAP_REQUIRE(b && path && n >= 0 && cons_index >= 0, "bed_write_locations: bad arguments");
@@ -507,19 +438,10 @@ static int bed_write_impl(const kmap_bed *b, const char *path, int cons_index, i
     const size_t per_row = b->max_chrom + b->max_strand + name0.size() + 3 * 21 + 8;
     const int64_t rows_per_chunk = 1 << 16;
     const int64_t n_chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-    struct Chunk {
-        std::unique_ptr<char[]> mem;
-        size_t len = 0;
-    };
-    std::vector<Chunk> bufs((size_t)n_chunks);
-    std::atomic<bool> oom{false};
-    run_parallel((size_t)n_chunks, b->threads, [&](size_t ch) {
+    std::vector<KmapChunk> bufs((size_t)n_chunks);
+    kmap_parallel_for((size_t)n_chunks, b->threads, [&](size_t ch) {
         const int64_t lo = (int64_t)ch * rows_per_chunk, hi = std::min(n, lo + rows_per_chunk);
-        char *p0 = new (std::nothrow) char[(size_t)(hi - lo) * per_row];
-        if (!p0) {
-            oom = true;
-            return;
-        }
+        char *const p0 = new char[(size_t)(hi - lo) * per_row];   // a bad_alloc here is the ABI handler's
         bufs[ch].mem.reset(p0);
         char *p = p0;
         for (int64_t i = lo; i < hi; ++i) {
@@ -528,12 +450,12 @@ static int bed_write_impl(const kmap_bed *b, const char *path, int cons_index, i
             memcpy(p, c.data(), c.size());
             p += c.size();
             *p++ = '\t';
-            p = put_i64(p, start[i]);
+            p = kmap_put_int(p, start[i]);
             *p++ = '\t';
-            p = put_i64(p, end[i]);
+            p = kmap_put_int(p, end[i]);
             memcpy(p, name0.data(), name0.size());
             p += name0.size();
-            p = put_i64(p, r);
+            p = kmap_put_int(p, r);
             memcpy(p, "\t0\t", 3);
             p += 3;
             const std::string &s = b->strands[b->strand[(size_t)r]];
@@ -543,38 +465,17 @@ static int bed_write_impl(const kmap_bed *b, const char *path, int cons_index, i
         }
         bufs[ch].len = (size_t)(p - p0);
     });
-    if (oom) {
-        kmap_set_error("bed_write_locations: out of memory");
-        return KMAP_E_NOMEM;
-    }
-    const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
-    if (fd < 0) {
+    KmapFd out(open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666));
+    if (out.fd < 0) {
         kmap_set_error("bed_write_locations: cannot open %s: %s", path, strerror(errno));
         return KMAP_E_IO;
     }
-    std::vector<int64_t> off((size_t)n_chunks + 1, (int64_t)header.size());
-    for (int64_t ch = 0; ch < n_chunks; ++ch) off[(size_t)ch + 1] = off[(size_t)ch] + (int64_t)bufs[(size_t)ch].len;
-    std::atomic<bool> ok{true};
-    auto put = [&](const char *src, size_t left, int64_t at) {
-        while (left) {
-            const ssize_t w = pwrite(fd, src, left, (off_t)at);
-            if (w <= 0) {
-                ok = false;
-                return;
-            }
-            src += w;
-            at += w;
-            left -= (size_t)w;
-        }
-    };
-    put(header.data(), header.size(), 0);
-    run_parallel((size_t)n_chunks, std::min(b->threads, 2u), [&](size_t ch) { put(bufs[ch].mem.get(), bufs[ch].len, off[ch]); });   // one inode lock
-    const int rc = close(fd);
-    if (rc != 0 || !ok) {
+    const int64_t end_off = kmap_pwrite_all(out.fd, header.data(), header.size(), 0) ? kmap_write_chunks(out.fd, (int64_t)header.size(), bufs, b->threads) : -1;
+    if (out.close() != 0 || end_off < 0) {
         kmap_set_error("bed_write_locations: write to %s failed: %s", path, strerror(errno));
         return KMAP_E_IO;
     }
-    if (bytes_written) *bytes_written = off.back();
+    if (bytes_written) *bytes_written = end_off;
     return KMAP_OK;
 }
 

@@ -5,14 +5,11 @@
 #include <zlib.h>
 #include <stdio.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
 #include <cmath>
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -22,50 +19,7 @@
 #include <vector>
 
 #include "common.h"
-
-namespace {
-// decimal text of 0..9999: four characters (left-aligned, and zero-padded) + the length of the unpadded form.  The CSV rows
-// are nothing but small integers -- read index, positions < read length, read length -- so one lookup and one 4-byte store
-// per number replaces the digit loop (8 M rows per file at C3: 50 -> ~15 ns per row and core)
-struct Dec4 {
-    char plain[10000][4];
-    char padded[10000][4];
-    unsigned char len[10000];
-    Dec4() {
-        for (int v = 0; v < 10000; ++v) {
-            const char d[4] = {(char)('0' + v / 1000), (char)('0' + v / 100 % 10), (char)('0' + v / 10 % 10), (char)('0' + v % 10)};
-            const int skip = v >= 1000 ? 0 : v >= 100 ? 1 : v >= 10 ? 2 : 3;
-            for (int i = 0; i < 4; ++i) {
-                padded[v][i] = d[i];
-                plain[v][i] = i + skip < 4 ? d[i + skip] : '0';
-            }
-            len[v] = (unsigned char)(4 - skip);
-        }
-    }
-};
-const Dec4 g_dec4;
-
-// append the decimal form of v to buf (which has >= 4 bytes of slack behind the number), return the new end
-inline char *put_int(char *p, long long v) {
-    if (v >= 0 && v < 10000) {
-        memcpy(p, g_dec4.plain[v], 4);
-        return p + g_dec4.len[v];
-    }
-    if (v >= 0 && v < 100000000) {
-        const int hi = (int)(v / 10000), lo = (int)(v % 10000);
-        memcpy(p, g_dec4.plain[hi], 4);
-        p += g_dec4.len[hi];
-        memcpy(p, g_dec4.padded[lo], 4);
-        return p + 4;
-    }
-    if (v < 0) { *p++ = '-'; v = -v; }
-    char tmp[24];
-    int n = 0;
-    do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-    while (n) *p++ = tmp[--n];
-    return p;
-}
-}  // namespace
+#include "host_pool.h"
 
 namespace {
 template <typename HT>
@@ -73,158 +27,105 @@ int write_occurrence_csv_impl(const char *path, const char *header, int64_t n_se
                               const int32_t *const *pos, const int64_t *read_len, int64_t *rows_written) {
     KMAP_REQUIRE(path && header && n_seq >= 0 && n_cons >= 0, "write_occurrence_csv: bad arguments");
     KMAP_REQUIRE(n_seq == 0 || n_cons == 0 || (hits && pos && read_len), "write_occurrence_csv: null arrays");
-    FILE *fh = fopen(path, "w");
-    if (!fh) {
+    KmapFd out(open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666));
+    if (out.fd < 0) {
         kmap_set_error("write_occurrence_csv: cannot open %s: %s", path, strerror(errno));
         return KMAP_E_INVAL;
     }
-    fputs(header, fh);
-    fputc('\n', fh);
+    const std::string head = std::string(header) + "\n";
     // format in parallel: reads are cut into chunks, every chunk gets its own cursor (prefix of hits) and buffer,
     // buffers are written in chunk order
-    static const int thread_cap = getenv("KMAP_IO_THREADS") ? std::max(1, atoi(getenv("KMAP_IO_THREADS"))) : 16;   // several writers run at once (scan_motif)
-    const int n_threads = (int)std::min<int64_t>(std::max<unsigned>(1u, std::thread::hardware_concurrency()), thread_cap);
+    const unsigned n_threads = kmap_io_threads();
     const int64_t n_chunks = std::max<int64_t>(1, std::min<int64_t>((n_seq + 65535) / 65536, 4096));
     const int64_t per = (n_seq + n_chunks - 1) / n_chunks;
     std::vector<std::vector<int64_t>> start((size_t)n_chunks, std::vector<int64_t>((size_t)n_cons, 0));
-    {   // per-chunk hit sums in parallel, then a serial prefix over the (few thousand) chunks
-        std::atomic<int64_t> nx{0};
-        auto sum_worker = [&]() {
-            for (;;) {
-                const int64_t ch = nx.fetch_add(1);
-                if (ch >= n_chunks) return;
-                const int64_t lo = ch * per, hi = std::min(n_seq, lo + per);
-                for (int c = 0; c < n_cons; ++c) {
-                    int64_t s2 = 0;
-                    for (int64_t i = lo; i < hi; ++i) s2 += hits[c][i];
-                    start[(size_t)ch][(size_t)c] = s2;
-                }
-            }
-        };
-        std::vector<std::thread> pool;
-        for (int t = 0; t < n_threads; ++t) pool.emplace_back(sum_worker);
-        for (auto &t : pool) t.join();
-        std::vector<int64_t> cur((size_t)n_cons, 0);
-        for (int64_t ch = 0; ch < n_chunks; ++ch)
-            for (int c = 0; c < n_cons; ++c) {
-                const int64_t s2 = start[(size_t)ch][(size_t)c];
-                start[(size_t)ch][(size_t)c] = cur[(size_t)c];
-                cur[(size_t)c] += s2;
-            }
-    }
-    // uninitialised buffers: a vector<char>::resize would zero-fill (and page-fault) every byte before it is formatted over
-    struct Chunk {
-        std::unique_ptr<char[]> mem;
-        size_t len = 0;
-        char *data() const { return mem.get(); }
-        size_t size() const { return len; }
-        bool empty() const { return len == 0; }
-    };
-    std::vector<Chunk> bufs((size_t)n_chunks);
-    std::vector<int64_t> rows_of((size_t)n_chunks, 0);
-    std::atomic<int64_t> next{0};
-    auto worker = [&]() {
-        for (;;) {
-            const int64_t ch = next.fetch_add(1);
-            if (ch >= n_chunks) return;
-            const int64_t lo = ch * per, hi = std::min(n_seq, lo + per);
-            std::vector<int64_t> cursor = start[(size_t)ch];
-            Chunk &buf = bufs[(size_t)ch];
-            size_t need = 0;
-            for (int64_t i = lo; i < hi; ++i) {
-                size_t r = 48;
-                for (int c = 0; c < n_cons; ++c) r += 12 * (size_t)hits[c][i] + 2;
-                need += r;
-            }
-            buf.mem.reset(new char[need + 64]);
-            char *p = buf.data();
-            int64_t rows = 0;
-            for (int64_t i = lo; i < hi; ++i) {
-                bool any = false;
-                for (int c = 0; c < n_cons; ++c) any |= hits[c][i] > 0;
-                if (any) {
-                    p = put_int(p, i);
-                    for (int c = 0; c < n_cons; ++c) {
-                        *p++ = ';';
-                        const int32_t *q = pos[c] + cursor[(size_t)c];
-                        for (int32_t h = 0; h < (int32_t)hits[c][i]; ++h) {
-                            if (h) *p++ = ',';
-                            p = put_int(p, q[h]);
-                        }
-                    }
-                    *p++ = ';';
-                    p = put_int(p, read_len[i]);
-                    *p++ = '\n';
-                    ++rows;
-                }
-                for (int c = 0; c < n_cons; ++c) cursor[(size_t)c] += hits[c][i];
-            }
-            buf.len = (size_t)(p - buf.data());
-            rows_of[(size_t)ch] = rows;
+    // per-chunk hit sums in parallel, then a serial prefix over the (few thousand) chunks
+    kmap_parallel_for((size_t)n_chunks, n_threads, [&](size_t ch) {
+        const int64_t lo = (int64_t)ch * per, hi = std::min(n_seq, lo + per);
+        for (int c = 0; c < n_cons; ++c) {
+            int64_t s2 = 0;
+            for (int64_t i = lo; i < hi; ++i) s2 += hits[c][i];
+            start[ch][(size_t)c] = s2;
         }
-    };
-    {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < n_threads; ++t) pool.emplace_back(worker);
-        for (auto &t : pool) t.join();
-    }
-    // the chunks go to their final offsets with parallel pwrite()s (one memcpy into the page cache per thread instead of
-    // one serial stream: 185 MB per file at C3)
-    int64_t rows = 0;
-    fflush(fh);
-    const int fd = fileno(fh);
-    std::vector<int64_t> off((size_t)n_chunks + 1, 0);
-    off[0] = (int64_t)ftello(fh);
-    for (int64_t ch = 0; ch < n_chunks; ++ch) {
-        off[(size_t)ch + 1] = off[(size_t)ch] + (int64_t)bufs[(size_t)ch].size();
-        rows += rows_of[(size_t)ch];
-    }
-    std::atomic<bool> write_ok{true};
-    {
-        std::atomic<int64_t> nx{0};
-        auto write_worker = [&]() {
-            for (;;) {
-                const int64_t ch = nx.fetch_add(1);
-                if (ch >= n_chunks) return;
-                const char *src = bufs[(size_t)ch].data();
-                size_t left = bufs[(size_t)ch].size();
-                int64_t at = off[(size_t)ch];
-                while (left) {
-                    const ssize_t w = pwrite(fd, src, left, (off_t)at);
-                    if (w <= 0) {
-                        write_ok = false;
-                        return;
+    });
+    std::vector<int64_t> cur((size_t)n_cons, 0);
+    for (int64_t ch = 0; ch < n_chunks; ++ch)
+        for (int c = 0; c < n_cons; ++c) {
+            const int64_t s2 = start[(size_t)ch][(size_t)c];
+            start[(size_t)ch][(size_t)c] = cur[(size_t)c];
+            cur[(size_t)c] += s2;
+        }
+    std::vector<KmapChunk> bufs((size_t)n_chunks);
+    std::vector<int64_t> rows_of((size_t)n_chunks, 0);
+    kmap_parallel_for((size_t)n_chunks, n_threads, [&](size_t ch) {
+        const int64_t lo = (int64_t)ch * per, hi = std::min(n_seq, lo + per);
+        std::vector<int64_t> cursor = start[ch];
+        KmapChunk &buf = bufs[ch];
+        size_t need = 0;
+        for (int64_t i = lo; i < hi; ++i) {
+            size_t r = 48;
+            for (int c = 0; c < n_cons; ++c) r += 12 * (size_t)hits[c][i] + 2;
+            need += r;
+        }
+        buf.mem.reset(new char[need + 64]);
+        char *p = buf.mem.get();
+        int64_t rows = 0;
+        for (int64_t i = lo; i < hi; ++i) {
+            bool any = false;
+            for (int c = 0; c < n_cons; ++c) any |= hits[c][i] > 0;
+            if (any) {
+                p = kmap_put_int(p, i);
+                for (int c = 0; c < n_cons; ++c) {
+                    *p++ = ';';
+                    const int32_t *q = pos[c] + cursor[(size_t)c];
+                    for (int32_t h = 0; h < (int32_t)hits[c][i]; ++h) {
+                        if (h) *p++ = ',';
+                        p = kmap_put_int(p, q[h]);
                     }
-                    src += w;
-                    at += w;
-                    left -= (size_t)w;
                 }
+                *p++ = ';';
+                p = kmap_put_int(p, read_len[i]);
+                *p++ = '\n';
+                ++rows;
             }
-        };
-        std::vector<std::thread> pool;
-        for (int t = 0; t < std::min(n_threads, 2); ++t) pool.emplace_back(write_worker);   // one inode lock: more threads only wait (measured 4..64: 21-27 ms)
-        for (auto &t : pool) t.join();
-    }
-    const int rc = fclose(fh);
+            for (int c = 0; c < n_cons; ++c) cursor[(size_t)c] += hits[c][i];
+        }
+        buf.len = (size_t)(p - buf.mem.get());
+        rows_of[ch] = rows;
+    });
+    int64_t rows = 0;
+    for (int64_t r : rows_of) rows += r;
+    const bool ok = kmap_pwrite_all(out.fd, head.data(), head.size(), 0) && kmap_write_chunks(out.fd, (int64_t)head.size(), bufs, n_threads) >= 0;
+    const int rc = out.close();
     if (rows_written) *rows_written = rows;
-    if (rc != 0 || !write_ok) {
+    if (rc != 0 || !ok) {
         kmap_set_error("write_occurrence_csv: write to %s failed", path);
         return KMAP_E_INVAL;
     }
     return KMAP_OK;
+}
+template <typename HT>
+int write_occurrence_csv_abi(const char *path, const char *header, int64_t n_seq, int n_cons, const HT *const *hits,
+                             const int32_t *const *pos, const int64_t *read_len, int64_t *rows_written) {
+    try {                                              // no C++ exception crosses the C ABI (a formatting thread's bad_alloc arrives here)
+        return write_occurrence_csv_impl<HT>(path, header, n_seq, n_cons, hits, pos, read_len, rows_written);
+    } catch (const std::bad_alloc &) {
+        kmap_set_error("write_occurrence_csv: out of memory");
+        return KMAP_E_NOMEM;
+    }
 }
 }  // namespace
 
 extern "C" int kmap_write_occurrence_csv(const char *path, const char *header, int64_t n_seq, int n_cons,
                                          const int32_t *const *hits, const int32_t *const *pos, const int64_t *read_len,
                                          int64_t *rows_written) {
-    return write_occurrence_csv_impl<int32_t>(path, header, n_seq, n_cons, hits, pos, read_len, rows_written);
+    return write_occurrence_csv_abi<int32_t>(path, header, n_seq, n_cons, hits, pos, read_len, rows_written);
 }
 // same file from byte-sized hit counts (kmap_scan_fetch_stream_u8: a quarter of the bytes to fetch and to walk)
 extern "C" int kmap_write_occurrence_csv_u8(const char *path, const char *header, int64_t n_seq, int n_cons,
                                             const uint8_t *const *hits, const int32_t *const *pos, const int64_t *read_len,
                                             int64_t *rows_written) {
-    return write_occurrence_csv_impl<uint8_t>(path, header, n_seq, n_cons, hits, pos, read_len, rows_written);
+    return write_occurrence_csv_abi<uint8_t>(path, header, n_seq, n_cons, hits, pos, read_len, rows_written);
 }
 
 // ---- "%.2f" rows (the co-occurrence distance file, reference motif_discovery.py:1143-1162) ---------------------------------
@@ -241,7 +142,7 @@ inline char *put_f2(char *p, double v) {
             *p++ = '-';
             h = -h;
         }
-        p = put_int(p, h >> 1);
+        p = kmap_put_int(p, h >> 1);
         *p++ = '.';
         *p++ = (h & 1) ? '5' : '0';
         *p++ = '0';
@@ -260,44 +161,17 @@ static int write_f2_tsv_line_impl(int fd, const double *v, int64_t n) {
     const int64_t per = 1 << 16;
     const int64_t n_chunks = (n + per - 1) / per;
     std::vector<std::string> parts((size_t)std::max<int64_t>(n_chunks, 1));
-    static const int thread_cap = getenv("KMAP_IO_THREADS") ? std::max(1, atoi(getenv("KMAP_IO_THREADS"))) : 16;
-    const int n_threads = (int)std::min<int64_t>(std::min<int64_t>(std::max<unsigned>(1u, std::thread::hardware_concurrency()), thread_cap),
-                                                 std::max<int64_t>(n_chunks, 1));
-    std::atomic<int64_t> next{0};
-    std::atomic<int> oom{0};
-    auto worker = [&]() {
+    kmap_parallel_for((size_t)n_chunks, kmap_io_threads(), [&](size_t c) {   // a bad_alloc here is the ABI handler's
         char tmp[352];
-        for (;;) {
-            const int64_t c = next.fetch_add(1);
-            if (c >= n_chunks) return;
-            const int64_t lo = c * per, hi = std::min(n, lo + per);
-            try {
-                std::string &out = parts[(size_t)c];
-                out.reserve((size_t)(hi - lo) * 8);
-                for (int64_t i = lo; i < hi; ++i) {
-                    char *e = put_f2(tmp, v[i]);
-                    *e++ = (i + 1 == n) ? '\n' : '\t';
-                    out.append(tmp, (size_t)(e - tmp));
-                }
-            } catch (...) {
-                oom.store(1);
-                return;
-            }
+        const int64_t lo = (int64_t)c * per, hi = std::min(n, lo + per);
+        std::string &out = parts[c];
+        out.reserve((size_t)(hi - lo) * 8);
+        for (int64_t i = lo; i < hi; ++i) {
+            char *e = put_f2(tmp, v[i]);
+            *e++ = (i + 1 == n) ? '\n' : '\t';
+            out.append(tmp, (size_t)(e - tmp));
         }
-    };
-    {
-        std::vector<std::thread> pool;
-        try {
-            for (int t = 1; t < n_threads; ++t) pool.emplace_back(worker);
-        } catch (...) {
-        }
-        worker();
-        for (auto &th : pool) th.join();
-    }
-    if (oom.load()) {
-        kmap_set_error("write_f2_tsv_line: out of memory");
-        return KMAP_E_NOMEM;
-    }
+    });
     if (n == 0) parts[0] = "\n";
     for (const std::string &part : parts) {
         const char *p = part.data();
@@ -463,8 +337,8 @@ struct FaRange {                        // a range of the mapped file and what k
 
 struct kmap_fasta {
     // mapped plain file
-    const uint8_t *map = nullptr;
-    size_t map_len = 0;
+    KmapMappedFile file;
+    const uint8_t *map() const { return (const uint8_t *)file.p; }
     std::vector<FaRange> ranges;
     size_t first_range = 0;             // the range that holds the first header of the file; earlier ranges are text to ignore
     // gzip stream: the whole encoding (header 255s included) + their positions
@@ -473,37 +347,10 @@ struct kmap_fasta {
     std::vector<size_t> seps;
     int64_t n_bytes = 0, n_seq = 0;
     unsigned threads = 1;
-    ~kmap_fasta() {
-        if (map) munmap((void *)map, map_len);
-        free(buf);
-    }
+    ~kmap_fasta() { free(buf); }
 };
 
 namespace {
-unsigned fa_threads() {
-    const char *v = getenv("KMAP_IO_THREADS");
-    const int cap = v ? std::max(1, atoi(v)) : 16;
-    return (unsigned)std::min<int>((int)std::max(1u, std::thread::hardware_concurrency()), cap);
-}
-// fn(t) for t in [0, n) on up to `nt` threads (the calling thread takes its share; threads that cannot be started are not missed)
-template <typename F>
-void fa_parallel(size_t n, unsigned nt, F fn) {
-    std::atomic<size_t> next{0};
-    auto worker = [&]() {
-        for (;;) {
-            const size_t t = next.fetch_add(1);
-            if (t >= n) return;
-            fn(t);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (unsigned i = 1; i < nt && i < n; ++i) pool.emplace_back(worker);
-    } catch (...) {
-    }
-    worker();
-    for (auto &th : pool) th.join();
-}
 bool fa_reserve(kmap_fasta *f, size_t want) {   // room for `want` more bytes in the stream buffer
     if (f->len + want <= f->cap) return true;
     size_t ncap = f->cap + f->cap / 2;
@@ -630,60 +477,41 @@ int fa_open_stream(const char *path, kmap_fasta *f, size_t size_hint) {
 static int fasta_open_impl(const char *path, kmap_fasta **out, int64_t *n_bytes, int64_t *n_seq) {
     KMAP_REQUIRE(path && out && n_bytes && n_seq, "fasta_open: null argument");
     std::unique_ptr<kmap_fasta> f(new kmap_fasta());
-    f->threads = fa_threads();
+    f->threads = kmap_io_threads();
     size_t gz_hint = 0;
-    {
-        const int fd = open(path, O_RDONLY | O_CLOEXEC);
-        if (fd < 0) {
-            kmap_set_error("fasta_open: cannot open %s: %s", path, strerror(errno));
-            return KMAP_E_INVAL;
-        }
-        struct stat sb;
-        unsigned char magic[2] = {0, 0};
-        if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0 && pread(fd, magic, 2, 0) >= 1) {
-            if (!(magic[0] == 0x1f && magic[1] == 0x8b)) {
-                void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
-                if (m != MAP_FAILED) {
-                    f->map = (const uint8_t *)m;
-                    f->map_len = (size_t)sb.st_size;
-                }
-            } else if (sb.st_size >= 18) {                      // gzip trailer: ISIZE, the uncompressed length modulo 2^32
-                unsigned char t[4];
-                // trusted only as far as it is plausible for one member (deflate does not shrink text below ~1 / 1000 of its size)
-                if (pread(fd, t, 4, sb.st_size - 4) == 4) {
-                    const size_t isize = (size_t)t[0] | ((size_t)t[1] << 8) | ((size_t)t[2] << 16) | ((size_t)t[3] << 24);
-                    if (isize / 1024 <= (size_t)sb.st_size) gz_hint = isize;
-                }
+    KmapMappedFile &in = f->file;
+    if (!in.open(path)) {
+        kmap_set_error("fasta_open: cannot open %s: %s", path, strerror(errno));
+        return KMAP_E_INVAL;
+    }
+    unsigned char magic[2] = {0, 0};
+    if (in.n > 0 && pread(in.file.fd, magic, 2, 0) >= 1) {
+        if (!(magic[0] == 0x1f && magic[1] == 0x8b)) {
+            in.map();
+        } else if (in.n >= 18) {                                // gzip trailer: ISIZE, the uncompressed length modulo 2^32
+            unsigned char t[4];
+            // trusted only as far as it is plausible for one member (deflate does not shrink text below ~1 / 1000 of its size)
+            if (pread(in.file.fd, t, 4, (off_t)in.n - 4) == 4) {
+                const size_t isize = (size_t)t[0] | ((size_t)t[1] << 8) | ((size_t)t[2] << 16) | ((size_t)t[3] << 24);
+                if (isize / 1024 <= in.n) gz_hint = isize;
             }
         }
-        close(fd);
     }
-    if (!f->map) {
+    (void)in.file.close();
+    if (!f->map()) {
         KMAP_TRY(fa_open_stream(path, f.get(), gz_hint));
     } else {
         // ranges of >= KMAP_FASTA_MIN_CHUNK bytes (default 4 MiB; the tests cut small files finer), each cut behind a newline
         const char *mc = getenv("KMAP_FASTA_MIN_CHUNK");
         const size_t min_chunk = mc ? (size_t)std::max(1ll, atoll(mc)) : ((size_t)4 << 20);
-        const size_t n = f->map_len;
-        const size_t want = std::max<size_t>(1, std::min<size_t>((size_t)f->threads * 4, n / min_chunk));
-        std::vector<size_t> cut;
-        cut.push_back(0);
-        for (size_t t = 1; t < want; ++t) {
-            const size_t from = std::max(cut.back(), (n / want) * t);
-            if (from >= n) break;
-            const uint8_t *nl = (const uint8_t *)memchr(f->map + from, '\n', n - from);
-            if (!nl || (size_t)(nl - f->map) + 1 >= n) break;
-            const size_t at = (size_t)(nl - f->map) + 1;
-            if (at > cut.back()) cut.push_back(at);
-        }
-        cut.push_back(n);
+        const std::vector<size_t> cut = kmap_cut_lines(in.p, 0, in.n, f->threads, min_chunk);
         f->ranges.resize(cut.size() - 1);
-        fa_parallel(f->ranges.size(), f->threads, [&](size_t i) {
+        kmap_parallel_for(f->ranges.size(), f->threads, [&](size_t i) {
             FaRange &r = f->ranges[i];
             r.lo = cut[i];
             r.hi = cut[i + 1];
             FaState st;
-            r.out = fa_walk<false>(f->map + r.lo, r.hi - r.lo, st, nullptr, 0, FA_OVERRUN, [&](size_t in_at, size_t out_at) {
+            r.out = fa_walk<false>(f->map() + r.lo, r.hi - r.lo, st, nullptr, 0, FA_OVERRUN, [&](size_t in_at, size_t out_at) {
                 if (r.headers++ == 0) {
                     r.first_hdr_in = in_at;
                     r.first_hdr_out = out_at;
@@ -738,11 +566,11 @@ static int fasta_read_impl(kmap_fasta *f, uint8_t *seq_out, int64_t *borders_out
     };
     borders_out[0] = 0;
     std::atomic<int> changed{0};
-    if (f->map) {
-        fa_parallel(f->ranges.size() - f->first_range, f->threads, [&](size_t j) {
+    if (f->map()) {
+        kmap_parallel_for(f->ranges.size() - f->first_range, f->threads, [&](size_t j) {
             const size_t i = f->first_range + j;
             const FaRange &r = f->ranges[i];
-            const uint8_t *p = f->map + r.lo;
+            const uint8_t *p = f->map() + r.lo;
             size_t n = r.hi - r.lo, rank = r.rank0;
             FaState st;
             if (i == f->first_range) {                      // from behind the '>' of the file's first header: rank 0 writes nothing

@@ -6,13 +6,18 @@
 //   driver csv <out_i32.csv> <out_u8.csv> <n_seq> <seed>    the same synthetic hit lists through both CSV entry points
 //   driver pool <n>                                         u32 -> i64 (unaligned destination), u32 -> u64, u32 -> u32 conversions
 //   driver f2 <values.f64> <out.tsv> <medians.f64>          the "%.2f" line writer of the co-occurrence file and the per-read medians
+//   driver par | cut | int                                  kmap_parallel_for (every index once; a body's exception), kmap_cut_lines
+//                                                           (the ranges' properties), kmap_put_int (against snprintf) of host_pool.h
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <cmath>
+#include <new>
+#include <string>
 #include <vector>
 
 #include "../../include/kmap_hip.h"
@@ -155,6 +160,86 @@ int main(int argc, char **argv) {
         printf("%zu %zu %zu\n", v.size(), hits.size(), pos.size());
         return 0;
     }
-    fprintf(stderr, "usage: driver fasta|csv|pool|f2 ...\n");
+    if (argc >= 2 && !strcmp(argv[1], "par")) {     // driver par: kmap_parallel_for visits every index once; an exception of the body ends on this thread
+        for (unsigned nt : {1u, 3u, 16u})
+            for (size_t n : {(size_t)0, (size_t)1, (size_t)nt - 1, (size_t)nt, (size_t)nt + 1, (size_t)100000}) {
+                std::vector<int> seen(n, 0);
+                kmap_parallel_for(n, nt, [&](size_t i) { ++seen[i]; });
+                for (size_t i = 0; i < n; ++i)
+                    if (seen[i] != 1) return fail("par: an index was not visited exactly once", (int)i);
+            }
+        const struct { size_t n, at; unsigned nt; } cases[] = {{10000, 5000, 8}, {10000, 0, 8}, {10000, 0, 1}};
+        for (const auto &c : cases) {
+            std::vector<int> seen(c.n, 0);
+            std::atomic<int> running{0};
+            bool caught = false;
+            try {
+                kmap_parallel_for(c.n, c.nt, [&](size_t i) {
+                    struct In { std::atomic<int> &r; In(std::atomic<int> &r_) : r(r_) { ++r; } ~In() { --r; } } in(running);
+                    ++seen[i];
+                    if (i == c.at) throw std::bad_alloc();
+                });
+            } catch (const std::bad_alloc &) {
+                caught = true;
+            }
+            if (!caught) return fail("par: the body's bad_alloc did not arrive on the calling thread", (int)c.nt);
+            if (running.load() != 0) return fail("par: a thread is still in the body after the call", running.load());
+            if (seen[c.at] != 1) return fail("par: the throwing index was not visited once", seen[c.at]);
+            size_t visited = 0;
+            for (size_t i = 0; i < c.n; ++i) {
+                if (seen[i] > 1) return fail("par: an index was visited twice", (int)i);
+                visited += (size_t)seen[i];
+            }
+            if (c.nt == 1 && visited != c.at + 1) return fail("par: one thread went on after its exception", (int)visited);
+        }
+        printf("ok\n");
+        return 0;
+    }
+    if (argc >= 2 && !strcmp(argv[1], "cut")) {     // driver cut: the ranges of kmap_cut_lines tile [lo, n) and begin behind newlines
+        std::vector<std::string> texts = {"", "abc", "\n\n\n", std::string((size_t)1 << 20, 'q') + "\nx\n", ""};
+        uint64_t x = 88172645463325252ull;
+        for (int l = 0; l < 10000; ++l) {
+            x = x * 6364136223846793005ull + 1442695040888963407ull;
+            texts.back() += std::string((size_t)((x >> 33) % 31), 'a') + "\n";
+        }
+        for (size_t ti = 0; ti < texts.size(); ++ti) {
+            const std::string &t = texts[ti];
+            const size_t n = t.size(), nl = t.find('\n');
+            for (size_t lo : {(size_t)0, nl == std::string::npos ? n : nl + 1})
+                for (size_t min_chunk : {(size_t)1, (size_t)64, (size_t)1 << 40})
+                    for (unsigned threads : {1u, 8u}) {
+                        const std::vector<size_t> cut = kmap_cut_lines(t.data(), lo, n, threads, min_chunk);
+                        if (cut.empty() || cut.front() != lo || cut.back() != n) return fail("cut: the cuts do not run from lo to n", (int)ti);
+                        if (cut.size() - 1 > 4 * (size_t)threads) return fail("cut: more than 4 ranges per thread", (int)ti);
+                        for (size_t i = 1; i < cut.size(); ++i) {
+                            if (cut[i] <= cut[i - 1]) return fail("cut: the cuts are not strictly ascending", (int)ti);
+                            if (i + 1 < cut.size() && t[cut[i] - 1] != '\n') return fail("cut: an interior cut is not behind a newline", (int)ti);
+                        }
+                    }
+        }
+        printf("ok\n");
+        return 0;
+    }
+    if (argc >= 2 && !strcmp(argv[1], "int")) {     // driver int: kmap_put_int against snprintf("%lld")
+        std::vector<int64_t> vals = {0, 9, 10, 999, 1000, 9999, 10000, 99999999, 100000000, -1, -10000, INT64_MAX, INT64_MIN};
+        uint64_t x = 0x9E3779B97F4A7C15ull;
+        for (int i = 0; i < 100000; ++i) {
+            x = x * 6364136223846793005ull + 1442695040888963407ull;
+            vals.push_back((int64_t)x >> (int)((x >> 7) % 64));      // every magnitude, both signs
+        }
+        for (int64_t v : vals) {
+            char got[32], want[32];
+            char *e = kmap_put_int(got, v);
+            const int len = snprintf(want, sizeof want, "%lld", (long long)v);
+            if (e - got != len || memcmp(got, want, (size_t)len) != 0) {
+                *e = 0;
+                fprintf(stderr, "driver: kmap_put_int wrote %s for %s\n", got, want);
+                return 2;
+            }
+        }
+        printf("%zu\n", vals.size());
+        return 0;
+    }
+    fprintf(stderr, "usage: driver fasta|csv|pool|f2|par|cut|int ...\n");
     return 64;
 }

@@ -1,6 +1,6 @@
 """CPU sanitizer runs of the threaded HOST code of libkmap_hip (round-3 verdict item: none existed).  tests/host_san/Makefile compiles
-kmap_amd/csrc/host_io.hip (FASTA / gz reader, occurrence-CSV formatter + pwrite pool) and kmap_amd/csrc/host_pool.h (the
-conversion pool of counts_io.hip's table fetch) host-only, once with -fsanitize=address,undefined and once with -fsanitize=thread, into
+kmap_amd/csrc/host_io.hip (FASTA / gz reader, occurrence-CSV formatter + pwrite pool) and kmap_amd/csrc/host_pool.h (the building
+blocks they share with host_bed.hip and counts_io.hip: parallel loop, conversion pool, line cutter, integer formatter) host-only, once with -fsanitize=address,undefined and once with -fsanitize=thread, into
 a small driver; any sanitizer report fails the run (non-zero exit, text on stderr).  The FASTA results are also compared with a
 Python restatement of the reference's array contract (kmer_count.py:244-347) on ragged / empty / CRLF / lowercase / over-long-line
 inputs and with the golden arrays of tests/test.fa.  GPU AddressSanitizer is not available on this pool: CPU only."""
@@ -210,6 +210,18 @@ def test_conversion_pool(drivers, san):
     """u32 -> i64 into an UNALIGNED destination (the memory-mapped pickle view of TableSaver), u32 -> u64, u32 -> u32, empty input"""
     assert int(_run(drivers[san], "pool", 2_500_000).strip()) == 2_500_000
     assert int(_run(drivers[san], "pool", 1000).strip()) == 1000
+
+
+@pytest.mark.parametrize("san", ["asan", "tsan"])
+def test_host_building_blocks(drivers, san):
+    """host_pool.h on its own: kmap_parallel_for visits every index exactly once for n around the thread count and ends a body's
+    bad_alloc on the calling thread with every thread joined (also when the calling thread is the only one); kmap_cut_lines'
+    ranges run from lo to n, strictly ascending, interior cuts behind a newline, at most 4 per thread (empty text, no newline,
+    only newlines, one 1-MiB line, 10 000 short lines; lo = 0 and behind the first line); kmap_put_int equals snprintf("%lld")
+    at the edges of its fast paths, at INT64_MIN / INT64_MAX and on 100 000 values of a fixed generator"""
+    assert _run(drivers[san], "par").strip() == "ok"
+    assert _run(drivers[san], "cut").strip() == "ok"
+    assert int(_run(drivers[san], "int").strip()) == 100_013
 
 
 @pytest.mark.parametrize("san,threads", [("asan", "16"), ("tsan", "8"), ("tsan", "1")])
