@@ -13,7 +13,11 @@
  *     thread-local message.
  *   - `*_dev` pointers are device (HBM) pointers; plain names are host pointers.  Host-pointer
  *     entry points are blocking.  Device-pointer entry points are asynchronous on `stream`
- *     (a hipStream_t passed as void*, NULL = default stream) unless stated otherwise.
+ *     (a hipStream_t passed as void*, NULL = default stream) unless stated otherwise.  An entry that returns a host value (a
+ *     number of entries, a total) waits for that value only: what it wrote to device memory, or keeps in its handle, is complete
+ *     in the order of `stream`, and a reader on ANOTHER stream -- the null stream included: streams of kmap_stream_create are
+ *     non-blocking -- needs kmap_stream_sync(stream) first.  Entry points without a stream argument that read device memory run
+ *     on the null stream; their comments say so.  tests/test_gpu_streams.py runs every stream-taking entry on such a stream.
  *   - the caller allocates every output (like the reference: np.empty then kernel); the library
  *     returns heap memory only behind opaque handles.
  *   - hashes are uint32 for k < 16 and uint64 for 16 <= k < 32, invalid hash = all ones,
@@ -123,7 +127,10 @@ int kmap_counts_run_hashes_dev(kmap_counts *c, const void *hash_dev, int64_t n, 
 /* load counts computed earlier (e.g. from kmer_count/k{k}.pkl, find_motif motif_discovery.py:621-624):
  * uniq uint32/uint64 by k, cnt int32/int64 by k, host arrays */
 int kmap_counts_load(kmap_counts *c, const void *uniq, const void *cnt, int64_t n_uniq, int k);
-/* uniq_out: uint32[n_uniq] (k<16) or uint64[n_uniq]; cnt_out: int32 (k<16) or int64 */
+/* uniq_out: uint32[n_uniq] (k<16) or uint64[n_uniq]; cnt_out: int32 (k<16) or int64.  Runs on the null stream; after work on
+ * another stream (the count itself: it returns n_uniq while the kernel that writes the table may still be in flight) call
+ * kmap_stream_sync on it first.  The same holds for kmap_counts_fetch_stream and kmap_counts_write_range on a stream other than
+ * the one the table was counted on. */
 int kmap_counts_fetch(kmap_counts *c, void *uniq_out, void *cnt_out);
 /* the same copy on a caller-chosen stream through pinned staging buffers (conversion on host threads): lets a background host
  * thread drain a finished table (multi-GB at k >= 14) while the default stream keeps counting into another handle */
@@ -137,6 +144,8 @@ int kmap_counts_write_range(kmap_counts *c, int which, int64_t first, int64_t co
  * histogram bins); valid until the next count / load / destroy on the handle.  Lets sample_disp_kmer (motif_discovery.py:812-921)
  * label a multi-GB table where it lies instead of re-reading k{k}.pkl */
 int kmap_counts_table_dev(kmap_counts *c, void **uniq_dev, void **cnt_dev, int64_t *n_uniq);
+/* kmap_counts_total, kmap_counts_topk and kmap_counts_hamball_mass run on the null stream; after work on another stream (the count
+ * that filled the table) call kmap_stream_sync on it first. */
 int kmap_counts_total(kmap_counts *c, int64_t *total);          /* sum of counts */
 /* the top_k (<= 16) most frequent k-mers: largest count first, ties by lowest index (np.argpartition's tie order,
  * motif_discovery.py:661, is numpy-specific; this rule is used when the arrays are too large to fetch per trial).
@@ -219,6 +228,11 @@ int kmap_scan_destroy(kmap_scan *s);
  * true.  Runs of this handle on the same border array then derive the borders from s instead of loading them (16 B per read).  The
  * declaration ends when the handle runs on other borders; renew it if the CONTENT of the array at that address changes. */
 int kmap_scan_declare_uniform(kmap_scan *s, const int64_t *borders_dev, int64_t n_seq, int64_t read_len, int64_t stride, int *accepted, void *stream);
+/* The run returns total_hits while the kernel that puts the positions in read order may still be in flight on `stream`:
+ * kmap_scan_summary must follow on the SAME stream (it synchronises behind that kernel) before any fetch on another stream --
+ * kmap_scan_fetch_stream[_u8] on a worker's stream, kmap_pwm_scan_fetch -- and before the handle runs again.  kmap_scan_fetch runs on
+ * the null stream (it synchronises the device first); after work on another stream call kmap_stream_sync on it first.  The same
+ * holds for kmap_pwm_scan_packed_dev. */
 int kmap_scan_run_packed_dev(kmap_scan *s, const uint32_t *codes_dev, const uint16_t *inval_dev, int64_t n,
                              const int64_t *borders_dev, int64_t n_seq, int k, uint64_t cons, int radius, int revcom,
                              int64_t *total_hits, const uint32_t *planes_dev /* optional, see above */, void *stream);
@@ -484,7 +498,10 @@ int kmap_pos_density(const int32_t *hits, const int64_t *offs, const int32_t *po
  * label n_cons when the minimum exceeds radius_k; members whose reverse complement is closer are re-oriented IN uniq_dev. */
 int kmap_label_kmers_dev(void *uniq_dev, int64_t n, int k, int n_cons, const uint64_t *cons_kh, const int32_t *cons_len,
                          const int32_t *cons_radius, int radius_k, int revcom_mode, uint8_t *label_dev, void *stream);
-/* per label l < n_labels (<= 64): sum of the counts (np.bincount weights) and number of members; cnt64 = 0: cnt is int32 (k < 16,
+/* kmap_label_sums_dev, kmap_prefix_search_dev, kmap_label_members_dev and kmap_gather_dev have no stream argument: they run on
+ * the null stream; after work on another stream (kmap_label_kmers_dev, kmap_label_prefix_dev or a count that produced their device
+ * arrays) call kmap_stream_sync on it first.
+ * per label l < n_labels (<= 64): sum of the counts (np.bincount weights) and number of members; cnt64 = 0: cnt is int32 (k < 16,
  * signed like the reference's), 1: int64, 2: the uint32 bins of a resident table with k >= 16 (zero-extended) */
 int kmap_label_sums_dev(const uint8_t *label_dev, const void *cnt_dev, int cnt64, int64_t n, int n_labels, int64_t *weight_sums,
                         int64_t *member_counts);
@@ -765,6 +782,10 @@ void *kmap_embed_coords_dev(kmap_embed *e);                                     
  * *n_bad = number of operands whose result differs, *first_bad_bits = the smallest such bit pattern. */
 int kmap_selftest_seq_div(int which, int rcp_steps, int quo_steps, uint32_t lo_bits, uint32_t hi_bits, uint64_t *n_bad,
                           uint32_t *first_bad_bits);
+/* a bounded delay on `stream` (test support of tests/_stream_order.py): one wave waits until the device's wall clock has advanced
+ * by ms milliseconds, sleeping in between, with a hard iteration cap, so that it ends even if the clock stood still.  It touches no
+ * memory.  Asynchronous on `stream`.  ms outside 1..100: KMAP_E_INVAL; a device without a wall clock rate: KMAP_E_UNSUP. */
+int kmap_selftest_delay_dev(int ms, void *stream);
 
 #ifdef __cplusplus
 }

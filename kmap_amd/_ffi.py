@@ -196,6 +196,7 @@ _SIGS = {
     "kmap_embed_get_losses": (i32, [vp, vp, i64, P(i64), vp]),
     "kmap_embed_coords_dev": (vp, [vp]),
     "kmap_selftest_seq_div": (i32, [i32, i32, i32, C.c_uint32, C.c_uint32, P(C.c_uint64), P(C.c_uint32)]),
+    "kmap_selftest_delay_dev": (i32, [i32, vp]),
 }
 
 

@@ -1,6 +1,7 @@
 // selftest.hip -- exhaustive device-side bit tests of arithmetic shortcuts the kernels rely on (test support; no reference
 // operator corresponds to it).  kmap_selftest_seq_div: for EVERY float bit pattern in [lo_bits, hi_bits], compare a candidate
-// division sequence of seq_div.h with the compiler's IEEE division.
+// division sequence of seq_div.h with the compiler's IEEE division.  kmap_selftest_delay_dev: a bounded timer that keeps a stream busy,
+// so that the stream-order tests can tell work that ran on the caller's stream from work that escaped to another one.
 #include "common.h"
 #include "seq_div.h"
 
@@ -42,9 +43,33 @@ __global__ __launch_bounds__(256) void seq_div_test_kernel(int which, int a, int
     if (mine) atomicAdd(bad, mine);
 }
 
+// One wave waits until the wall clock has advanced by `ticks`.  No memory is touched.  `max_iter` bounds the loop whatever the clock
+// does: one s_sleep(64) is about 4096 core cycles, so the cap is reached after a few times the requested delay at the latest.
+__global__ __launch_bounds__(64) void delay_kernel(uint64_t ticks, uint32_t max_iter) {
+    const uint64_t t0 = wall_clock64();
+    for (uint32_t it = 0; it < max_iter; ++it) {
+        if ((uint64_t)wall_clock64() - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(64);
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int kmap_selftest_delay_dev(int ms, void *stream) {
+    KMAP_REQUIRE(ms >= 1 && ms <= 100, "selftest_delay_dev: ms must be 1..100");
+    int dev = 0, khz = 0;
+    KMAP_CHECK_HIP(hipGetDevice(&dev));
+    KMAP_CHECK_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
+    if (khz <= 0) {
+        kmap_set_error("selftest_delay_dev: the device reports no wall clock rate");
+        return KMAP_E_UNSUP;
+    }
+    delay_kernel<<<1, 64, 0, as_stream(stream)>>>((uint64_t)khz * (uint64_t)ms, (uint32_t)ms * 2000u);
+    KMAP_CHECK_HIP(hipGetLastError());
+    return KMAP_OK;
+}
 
 int kmap_selftest_seq_div(int which, int rcp_steps, int quo_steps, uint32_t lo_bits, uint32_t hi_bits, uint64_t *n_bad,
                           uint32_t *first_bad_bits) {
