@@ -350,6 +350,26 @@ int kmap_readscore_counts_library_dev(const uint32_t *codes_dev, const uint16_t 
                                       uint64_t *counts_host /* n_mat x [4][32] */,
                                       int64_t *n_selected /* host, n_mat */, int64_t *n_minus /* host, n_mat */, void *stream);
 
+/* ---- erase the sites of a library of weight matrices from an invalid mask (discover_pwms --erase_rounds, erase_pwm_sites;
+ * csrc/pwm_erase.hip) -- not in the reference.  Matrices and their argument rules are
+ * kmap_readscore_library_dev's.  A hit of matrix m is kmap_pwm_scan_packed_dev's: a window of widths[m] positions, all valid under
+ * inval_eval_dev, whose score (with revcom the larger of the two strands') is thresholds[m] or more; every matrix is evaluated
+ * against inval_eval_dev as it is on entry.  cover_m = the positions inside at least one hit of m; n_hits[m] = the hits,
+ * n_covered[m] = |cover_m|; neither depends on the order of the matrices.  On return inval_out_dev holds what it held on entry
+ * with the bits of the union of the cover_m set, and *n_new = the bits that were 0 on entry and are 1 now.  inval_out_dev ==
+ * inval_eval_dev is allowed and means the same.  Only the (n + 15) / 16 data words of inval_out_dev are written -- nothing outside
+ * its kmap_packed_groups(n) words --, the codes never.  No borders: a valid window cannot cross the 255 behind every read.
+ * This entry has no stream argument: it runs on the null stream and is blocking (one synchronisation, behind the last kernel);
+ * after work on another stream that produced its device arrays call kmap_stream_sync on it first.  Integer counts only, so two
+ * calls give the same numbers; scratch memory only, no handle.  KMAP_E_INVAL: a width outside 4..31, a weight of 2^31 / 31 or
+ * more in magnitude or behind the width, a negative size, a NULL array.  n_mat == 0 or n == 0 gives zeros and leaves the mask as
+ * it is. */
+int kmap_erase_pwm_sites_dev(const uint32_t *codes_dev, const uint16_t *inval_eval_dev, int64_t n,
+                             int n_mat, const int32_t *widths /* host */, const int32_t *weights /* host, n_mat x [4][32] */,
+                             const int32_t *thresholds /* host, n_mat */, int revcom,
+                             uint16_t *inval_out_dev,
+                             int64_t *n_hits /* host, n_mat */, int64_t *n_covered /* host, n_mat */, int64_t *n_new /* host, one */);
+
 /* ---- at which distance and in which orientation the best site of every matrix of a library lies from a primary matrix's site
  * (motif_spacing; csrc/pwm_spacing.hip) -- not in the reference.  Matrices, batches and argument rules are
  * kmap_readscore_library_dev's.  prim_score_dev / prim_loc_dev / prim_strand_dev are kmap_readscore_packed_dev's three arrays for

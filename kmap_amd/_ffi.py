@@ -114,6 +114,7 @@ _SIGS = {
     "kmap_readscore_library_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "kmap_readscore_sites_library_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]),
     "kmap_readscore_counts_library_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "kmap_erase_pwm_sites_dev": (i32, [vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, P(i64)]),
     "kmap_readscore_spacing_library_dev": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp,
                                                  vp, vp]),
     "kmap_presence_library_dev": (i32, [vp, vp, i64, vp, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp]),

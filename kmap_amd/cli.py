@@ -25,7 +25,10 @@ than their own frequencies predict: one presence bit per motif and read, the sha
 hypergeometric z per pair, two-sided p-values and q-values (cooccurrence.py).  A twelfth, `discover_pwms`, makes the library the others
 consume: the k-mers most enriched against control reads become seeds, every seed grows from the Hamming ball around it into a
 count matrix by refine_pwm's iteration -- all seeds in lockstep, one batched counting pass over the reads per round --, and the
-matrices are evaluated against the control and grouped into families, one representative each (discover.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
+matrices are evaluated against the control and grouped into families, one representative each (discover.py); with `--erase_rounds R`
+it erases the sites of what a round found from reads and control and discovers again on what is left, so that a weaker motif behind
+a dominant one gets seeds of its own.  A thirteenth, `erase_pwm_sites`, is that erasure for a library of known motifs: every position
+inside a hit becomes N, and the reads that are left are written as FASTA for `preproc` (erase.py).  The reference's plotting / alignment verbs (draw_logo, align_conseq, plot_network) are out of scope here (SURVEY.md
 section 2).  `scan_motif` and `visualize_kmers` shard over the
 GPUs of a node when launched through `python -m torch.distributed.run --nproc-per-node G -m kmap_amd <verb> ...`."""
 import click
@@ -367,11 +370,38 @@ def motif_cooccurrence(res_dir, library_file, control_fasta_file=None, p_value=1
 @click.option("--family_e_value", type=float, default=0.01, required=False,
               help="two matrices are linked when each finds the other with an E-value of at most this")
 @click.option("--output_dir", type=str, default=None, required=False, help="Output directory (default: pwm_discovery in res_dir)")
+@click.option("--erase_rounds", type=int, default=1, required=False,
+              help="rounds of discovery, 1..16: after every round but the last the sites of the round's representatives are erased "
+                   "from reads and control, and the next round takes its seeds from what is left (1: no erasure)")
 def discover_pwms(res_dir, control_fasta_file, seed_len=8, n_seeds=64, seed_mismatches=1, seed_count=20, flank=2, min_count=2,
-                  p_value=1e-4, pseudocount=1.0, revcom_mode=None, max_iter=20, min_overlap=5, family_e_value=0.01, output_dir=None):
+                  p_value=1e-4, pseudocount=1.0, revcom_mode=None, max_iter=20, min_overlap=5, family_e_value=0.01, output_dir=None,
+                  erase_rounds=1):
     from .discover import _discover_pwms
+    rounds = () if erase_rounds == 1 else (erase_rounds,)        # one round is the call this verb has always made
     _discover_pwms(res_dir, control_fasta_file, seed_len, n_seeds, seed_mismatches, seed_count, flank, min_count, p_value, pseudocount,
-                   revcom_mode, max_iter, min_overlap, family_e_value, output_dir)
+                   revcom_mode, max_iter, min_overlap, family_e_value, output_dir, *rounds)
+
+
+@cli.command(name="erase_pwm_sites")
+@click.option("--res_dir", type=str, required=True, help="Result directory of preproc (holds config.toml and the encoded reads)")
+@click.option("--library_file", type=str, required=True, multiple=True,
+              help="motif library: a MEME minimal text file, a 4 x w base-count matrix CSV (as for evaluate_pwm), or a directory of "
+                   "*.meme and *.csv files; may be given several times")
+@click.option("--p_value", type=float, default=1e-4, required=False,
+              help="every window that reaches scan_pwm's threshold of this p-value is erased (per strand and per position)")
+@click.option("--min_score", type=float, default=None, required=False,
+              help="score threshold in bits; replaces the threshold derived from --p_value")
+@click.option("--pseudocount", type=float, default=1.0, required=False, help="pseudocount added to every column (a quarter per base)")
+@click.option("--nsites_default", type=int, default=20, required=False,
+              help="sites behind a MEME motif without nsites= (its probabilities become counts of this many sites)")
+@click.option("--revcom_mode", type=bool, default=None, required=False,
+              help="score both strands and erase on the better one's score (default: kmer_count.revcom_mode of config.toml)")
+@click.option("--output_file", type=str, default=None, required=False,
+              help="output FASTA file (default: erased_reads.fa in res_dir), a --fasta_file for preproc")
+def erase_pwm_sites(res_dir, library_file, p_value=1e-4, min_score=None, pseudocount=1.0, nsites_default=20, revcom_mode=None,
+                    output_file=None):
+    from .erase import _erase_pwm_sites
+    _erase_pwm_sites(res_dir, list(library_file), p_value, min_score, pseudocount, nsites_default, revcom_mode, output_file)
 
 
 @cli.command(name="shuffle_reads")

@@ -50,10 +50,13 @@ struct Grp {
     uint32_t c2;    // bases 32..47 (group g + 2)
     uint64_t m;     // 48 invalid flags, position 0 in bit 47
 };
-// groups at or behind n_data read as the halo does (all invalid); g + 1 and g + 2 of a data group lie inside the arrays (two halo groups)
+// groups at or behind n_data read as the halo does (all invalid); g + 1 and g + 2 of a data group lie inside the arrays (two halo groups).
+// SIGNED: the wave's first lanes may stand in front of the array (pwm_erase.hip: lanes 0 and 1 of the first tile hold groups -2 and -1);
+// a group in front of 0 reads as the halo does too
+template <bool SIGNED = false>
 __device__ __forceinline__ Grp load_grp(const uint32_t *__restrict__ codes, const uint16_t *__restrict__ inval, int64_t g, int64_t n_data,
                                         int lane) {
-    const bool in = g < n_data;
+    const bool in = (!SIGNED || g >= 0) && g < n_data;
     const uint32_t c0 = in ? codes[g] : 0u, m0 = in ? (uint32_t)inval[g] : 0xFFFFu;
     uint32_t c1 = __shfl_down(c0, 1), c2 = __shfl_down(c0, 2), m1 = __shfl_down(m0, 1), m2 = __shfl_down(m0, 2);
     if (lane >= KMAP_WAVE - 2) {           // the neighbours belong to the next wave's tile

@@ -319,19 +319,36 @@ class DeviceSeq:
                                                           ptr(Hlen), ptr(sites), ptr(too_long), None))
         return D.astype(np.int64), Hlen.astype(np.int64), sites, too_long
 
-    def library_counts(self, Ws, thresholds, revcom):
+    def library_counts(self, Ws, thresholds, revcom, use_work=False):
         """One refinement step for every weight matrix of Ws (int32 [4, width], widths may differ): the count matrix of the site
         reads' best windows (csrc/pwm_sites.hip).  Per matrix what pwm_counts(W, t, revcom,
         select_best=True) returns without n_hits, from library_sites' one pass over the original reads per batch of matrices:
         returns (list of int64[4, w_m]: C'[b][j] = selected windows whose oriented base j is b, n_selected int64[n_mat]: the site
-        reads, n_minus int64[n_mat]: those on '-').  Nothing per read leaves the device.  Needs no scan handle."""
+        reads, n_minus int64[n_mat]: those on '-').  Nothing per read leaves the device.  Needs no scan handle.  use_work: the
+        windows are those that are valid under the working mask (what mask() and erase_sites() left) instead of the original one."""
         n_mat, widths, weights, thr = _pack_library("library_counts", Ws, thresholds)
         counts = np.zeros((n_mat, 4, 32), np.uint64)
         n_sel, n_minus = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64)
-        check(_ffi.lib().kmap_readscore_counts_library_dev(self.codes.ptr, self.inval_orig.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,
+        inval = self.inval_work if use_work else self.inval_orig
+        check(_ffi.lib().kmap_readscore_counts_library_dev(self.codes.ptr, inval.ptr, self.n, self.borders.ptr, self.n_seq, n_mat,
                                                            ptr(widths), ptr(weights), ptr(thr), int(bool(revcom)), ptr(counts),
                                                            ptr(n_sel), ptr(n_minus), None))
         return [counts[m, :, :int(widths[m])].astype(np.int64) for m in range(n_mat)], n_sel, n_minus
+
+    def erase_sites(self, Ws, thresholds, revcom, use_work=True):
+        """Every position inside a hit of a weight matrix of Ws (int32 [4, width], widths may differ) becomes invalid in the working
+        mask (csrc/pwm_erase.hip).  A hit of matrix m is scan_pwm's: a window that scores thresholds[m] or
+        more (with revcom the larger of the two strands' scores) and touches no invalid position -- of the working mask as it is
+        on entry (use_work) or of the original one; every matrix sees that same mask.  Returns (n_hits int64[n_mat], n_covered
+        int64[n_mat]: the positions inside at least one hit of the matrix, n_new: the positions that were valid in the working mask
+        and are not any more).  Always writes inval_work, never the codes or inval_orig; reset() undoes it as it undoes mask().
+        Runs on the null stream and blocks.  Needs no scan handle."""
+        n_mat, widths, weights, thr = _pack_library("erase_sites", Ws, thresholds)
+        n_hits, n_cov, n_new = np.zeros(n_mat, np.int64), np.zeros(n_mat, np.int64), _ffi.i64(0)
+        inval = self.inval_work if use_work else self.inval_orig
+        check(_ffi.lib().kmap_erase_pwm_sites_dev(self.codes.ptr, inval.ptr, self.n, n_mat, ptr(widths), ptr(weights), ptr(thr),
+                                                  int(bool(revcom)), self.inval_work.ptr, ptr(n_hits), ptr(n_cov), C.byref(n_new)))
+        return n_hits, n_cov, n_new.value
 
     def library_spacing(self, primary, prim_width, prim_threshold, Ws, thresholds, revcom, max_gap=150):
         """For every weight matrix of Ws (int32 [4, width], widths may differ) at which distance and in which orientation its best

@@ -9,7 +9,10 @@ definition -- and whose later iterations are refine_pwm's.  All seeds are refine
 rank_motif_library does it, the results are matched all against all as match_motifs does it, and every family is represented by its
 member with the largest Mann-Whitney z.  The core takes its device work as callables, so it runs on any count, histogram and match
 function; host code is the loops, small-matrix arithmetic and the file formats.  The matrices are evaluated on the reads they were
-counted from, so mw_z is optimistic: a hold-out split is not made."""
+counted from, so mw_z is optimistic: a hold-out split is not made.  With --erase_rounds above 1 the sites
+of what a round found are erased from reads and control (DeviceSeq.erase_sites, csrc/pwm_erase.hip) and the next round takes its
+seeds and its counts from what is left, so that a weaker motif behind a dominant one gets seeds of its own; the evaluation stays
+on the original reads in every round."""
 import math
 from pathlib import Path
 
@@ -149,6 +152,14 @@ def discover_core(seeds, counts_fn, hist_fn, match_fn, revcom, flank=2, seed_mis
     Returns one dict per seed, in seed order: evaluate_histograms' fields plus seed_rank, name, seed, seed_fg, seed_control, seed_z,
     counts, status, trace, iterations, n_selected, n_minus, information_bits, family, family_size, is_representative, lo,
     fg_unscorable, control_unscorable, log10_p, q_bh, rank (its line in discovered_rank.csv)."""
+    out = refine_and_evaluate(seeds, counts_fn, hist_fn, flank, seed_mismatches, seed_count, p_value, pseudocount, max_iter, min_reads)
+    return group_and_rank(out, match_fn, revcom, min_overlap, pseudocount, family_e_value)
+
+
+def refine_and_evaluate(seeds, counts_fn, hist_fn, flank=2, seed_mismatches=1, seed_count=20, p_value=1e-4, pseudocount=1.0,
+                        max_iter=20, min_reads=10, first_index=0):
+    """discover_core's steps up to the evaluation for one list of seeds, numbered from first_index on: its dicts without q_bh, the
+    family fields and rank (threshold_p is pwm_threshold(W, p_value)[0] of the result's weights)"""
     seeds = [(str(s[0]), int(s[1]), int(s[2]), float(s[3])) for s in seeds]
     if not seeds:
         raise ValueError("discover_pwms: no seed: no k-mer is enriched in the reads (z > 0) at this seed_len and min_count")
@@ -160,7 +171,7 @@ def discover_core(seeds, counts_fn, hist_fn, match_fn, revcom, flank=2, seed_mis
         W = pwm_weights(C, pseudocount)
         t, lo, hi = pwm_threshold(W, p_value)
         if hi - lo + 1 > MAX_BINS:
-            raise ValueError(f"discover_pwms: seed {i}: scores from {lo} to {hi}: more than 2^22 different scores")
+            raise ValueError(f"discover_pwms: seed {first_index + i}: scores from {lo} to {hi}: more than 2^22 different scores")
         plans.append((W, t, lo, hi))
     Hf, fg_un, Hc, ctl_un = hist_fn([p[0] for p in plans], [p[2] for p in plans], [p[3] - p[2] + 1 for p in plans])
     out = []
@@ -168,11 +179,17 @@ def discover_core(seeds, counts_fn, hist_fn, match_fn, revcom, flank=2, seed_mis
         st = evaluate_histograms(Hf[i], Hc[i], lo, t, min_reads)
         last = trace[-1]
         built = [row for row in trace if row[2] > 0]             # the rounds with a selected window: the last one made the result
-        st.update(seed_rank=i, name=_field(f"seed{i}_{pwm_consensus(C)}"), seed=s[0], seed_fg=s[1], seed_control=s[2], seed_z=s[3],
+        idx = first_index + i
+        st.update(seed_rank=idx, name=_field(f"seed{idx}_{pwm_consensus(C)}"), seed=s[0], seed_fg=s[1], seed_control=s[2], seed_z=s[3],
                   counts=C, status=status, trace=trace, iterations=len(trace), n_selected=built[-1][2] if built else last[2],
                   n_minus=built[-1][3] if built else last[3], information_bits=information_bits(C, pseudocount), lo=lo,
                   fg_unscorable=int(fg_un[i]), control_unscorable=int(ctl_un[i]), log10_p=log10_p_of_z(st["mw_z"]))
         out.append(st)
+    return out
+
+
+def group_and_rank(out, match_fn, revcom, min_overlap=5, pseudocount=1.0, family_e_value=0.01):
+    """q_bh, the families with their representatives and rank over all of refine_and_evaluate's dicts, in place; returns them"""
     for st, q in zip(out, bh_qvalues([10.0 ** st["log10_p"] for st in out]).tolist()):
         st["q_bh"] = q
     fam = group_families([st["counts"] for st in out], [st["mw_z"] for st in out], match_fn, revcom, min_overlap, pseudocount,
@@ -184,7 +201,66 @@ def discover_core(seeds, counts_fn, hist_fn, match_fn, revcom, flank=2, seed_mis
     return out
 
 
+# ---- the rounds: discover, erase what was found, discover again ---------------------------------------------
+MAX_ERASE_ROUNDS = 16
+
+
+def check_erase_rounds(erase_rounds):
+    return _check_int("erase_rounds", erase_rounds, 1, MAX_ERASE_ROUNDS)
+
+
+def discover_rounds(seeds_fn, counts_fn, erase_fn, hist_fn, match_fn, revcom, erase_rounds=1, flank=2, seed_mismatches=1, seed_count=20,
+                    p_value=1e-4, pseudocount=1.0, max_iter=20, min_overlap=5, family_e_value=0.01, min_reads=10):
+    """discover_core in up to erase_rounds rounds with the found sites erased in between, on injected device work.
+    seeds_fn(round) -> [(kmer, fg_count, control_count, z)]: round 1 from the original reads and control, later rounds from what
+    the erasures left of both (select_seeds' use_work);
+    counts_fn(Ws, ts) in round 1, counts_fn(Ws, ts, use_work=True) in the later rounds: DeviceSeq.library_counts on the reads;
+    erase_fn(Ws, ts) -> (fg_hits[n], fg_covered[n], fg_new, control_hits[n], control_covered[n], control_new): DeviceSeq.erase_sites
+    (use_work=True) on the reads and on the control;
+    hist_fn and match_fn are discover_core's; hist_fn sees the original reads and the original control in every round, so mw_z is
+    comparable between rounds.
+    A round runs refine_and_evaluate on its seeds, numbered on from the round before.  After every round but the last the round's
+    own representatives (group_families over the round's matrices alone) that were built from at least one selected window are
+    erased: every hit at threshold_p.  The rounds end early when a later round has no seed, when a round has nothing to erase, or
+    when an erasure takes no position from the reads (the next round would be this one again); round 1 without a seed is
+    discover_core's ValueError.  q_bh, the families, their representatives and rank are group_and_rank's over the seeds of all
+    rounds: one match_fn call over the union.  Returns (results: discover_core's dicts plus `round`, in seed order; erase_log: one
+    dict per erasure: round, rows [(name, threshold, fg_hits, fg_covered, control_hits, control_covered)], fg_new, control_new).
+    With erase_rounds 1 the results are discover_core's and the log is empty."""
+    n_rounds = check_erase_rounds(erase_rounds)
+    results, erase_log = [], []
+    for r in range(1, n_rounds + 1):
+        seeds = list(seeds_fn(r))
+        if r > 1 and not seeds:
+            break
+        fn = counts_fn if r == 1 else (lambda Ws, ts: counts_fn(Ws, ts, use_work=True))
+        out = refine_and_evaluate(seeds, fn, hist_fn, flank, seed_mismatches, seed_count, p_value, pseudocount, max_iter, min_reads,
+                                  first_index=len(results))
+        for st in out:
+            st["round"] = r
+        results += out
+        if r == n_rounds:
+            break
+        _, _, is_rep = group_families([st["counts"] for st in out], [st["mw_z"] for st in out], match_fn, revcom, min_overlap,
+                                      pseudocount, family_e_value)
+        found = [st for st, rep in zip(out, is_rep) if rep and st["n_selected"] > 0]
+        if not found:
+            break
+        ts = [int(st["threshold_p"]) for st in found]
+        fh, fc, f_new, ch, cc, c_new = erase_fn([pwm_weights(st["counts"], pseudocount) for st in found], ts)
+        erase_log.append(dict(round=r, fg_new=int(f_new), control_new=int(c_new),
+                              rows=[(st["name"], t, int(a), int(b), int(c), int(d)) for st, t, a, b, c, d in zip(found, ts, fh, fc, ch, cc)]))
+        if int(f_new) == 0:
+            break
+    return group_and_rank(results, match_fn, revcom, min_overlap, pseudocount, family_e_value), erase_log
+
+
 # ---- files ------------------------------------------------------------------------------------------------------------------------
+ERASE_FILE = "discover_erase.csv"
+ERASE_HEADER = "round,name,threshold,fg_hits,fg_covered,control_hits,control_covered\n"
+ERASE_TOTALS_HEADER = "round,fg_new,control_new\n"
+
+
 def rank_line(st, pseudocount, revcom):
     """one line of discovered_rank.csv: pwm_eval.csv's columns from `width` on in eval_line's formatting, between the seed's own
     fields and its p and q"""
@@ -215,18 +291,31 @@ def meme_text(motifs, revcom=True):
     return "\n".join(lines) + "\n"
 
 
-def write_discovery(out_dir, results, pseudocount, revcom):
-    """the files of `kmap discover_pwms` from discover_core's results; returns the representatives in rank order"""
+def write_discovery(out_dir, results, pseudocount, revcom, erase_log=None):
+    """the files of `kmap discover_pwms` from discover_core's results; returns the representatives in rank order.  erase_log
+    (discover_rounds', for a run with --erase_rounds above 1; may be empty): discovered_rank.csv and discover_trace.csv get a last
+    column `round`, and discover_erase.csv lists what every erasure took: a row per erased matrix, and under them the positions
+    every erasure took from the reads and from the control."""
     out = Path(out_dir)
     (out / MATRIX_DIR).mkdir(parents=True, exist_ok=True)
     ranked = sorted(results, key=lambda st: st["rank"])
+
+    def with_round(text, st):
+        return text if erase_log is None else text[:-1] + f",{st['round']}\n"
     with open(out / RANK_FILE, "w") as fh:
-        fh.write(RANK_HEADER)
-        fh.write("".join(rank_line(st, pseudocount, revcom) for st in ranked))
+        fh.write(RANK_HEADER if erase_log is None else RANK_HEADER[:-1] + ",round\n")
+        fh.write("".join(with_round(rank_line(st, pseudocount, revcom), st) for st in ranked))
     with open(out / TRACE_FILE, "w") as fh:
-        fh.write(TRACE_HEADER)
+        fh.write(TRACE_HEADER if erase_log is None else TRACE_HEADER[:-1] + ",round\n")
         for st in results:
-            fh.write("".join(trace_line(st["seed_rank"], row) for row in st["trace"]))
+            fh.write("".join(with_round(trace_line(st["seed_rank"], row), st) for row in st["trace"]))
+    if erase_log is not None:
+        with open(out / ERASE_FILE, "w") as fh:
+            fh.write(ERASE_HEADER)
+            for e in erase_log:
+                fh.write("".join("%d,%s,%d,%d,%d,%d,%d\n" % ((e["round"],) + tuple(row)) for row in e["rows"]))
+            fh.write(ERASE_TOTALS_HEADER)
+            fh.write("".join(f"{e['round']},{e['fg_new']},{e['control_new']}\n" for e in erase_log))
     for st in results:
         np.savetxt(out / MATRIX_DIR / MATRIX_FILE.format(i=st["seed_rank"], consensus=pwm_consensus(st["counts"])), st["counts"],
                    delimiter=",", fmt="%d")
@@ -245,7 +334,7 @@ def _check_int(name, value, lo, hi=None):
 
 
 def check_arguments(seed_len=8, n_seeds=64, seed_mismatches=1, seed_count=20, flank=2, min_count=2, p_value=1e-4, pseudocount=1.0,
-                    max_iter=20, min_overlap=5, family_e_value=0.01):
+                    max_iter=20, min_overlap=5, family_e_value=0.01, erase_rounds=1):
     """every ValueError of the verb's numbers, each with its own message"""
     k = _check_int("seed_len", seed_len, MIN_WIDTH, MAX_WIDTH)
     f = _check_int("flank", flank, 0)
@@ -258,6 +347,7 @@ def check_arguments(seed_len=8, n_seeds=64, seed_mismatches=1, seed_count=20, fl
     _check_int("min_count", min_count, 1)
     _check_int("max_iter", max_iter, 1)
     _check_int("min_overlap", min_overlap, 1)
+    check_erase_rounds(erase_rounds)
     a = float(pseudocount)
     if not a > 0 or math.isinf(a):
         raise ValueError(f"pseudocount {pseudocount} is not a finite number > 0: the seed's empty flanks and zero counts need one")
@@ -268,16 +358,16 @@ def check_arguments(seed_len=8, n_seeds=64, seed_mismatches=1, seed_count=20, fl
     seed_threshold("A" * k, seed_count, f, seed_mismatches, a)          # the match weight lies above the mismatch weight
 
 
-def select_seeds(fg_seq, ctl_seq, k, dedupe, revcom, min_count, n_seeds):
+def select_seeds(fg_seq, ctl_seq, k, dedupe, revcom, min_count, n_seeds, use_work=False):
     """[(kmer, fg_count, control_count, z)]: enrich_kmers' counting and exact selection at length k, the selected rows in rank order
-    with z > 0, at most n_seeds"""
+    with z > 0, at most n_seeds; use_work: counted under the working masks of reads and control (what erase_sites left)"""
     from .enrichment import DeviceEnrich, count_both, select_enriched
     from .kmer_count import DeviceCounts, hash2kmer
     dc_f = dc_b = en = None
     try:
         dc_f, dc_b, en = DeviceCounts(), DeviceCounts(), DeviceEnrich()
-        _, Nf, Nb = count_both(fg_seq, ctl_seq, dc_f, dc_b, k, dedupe, revcom)
-        (_, kh, a, b, z), _ = select_enriched(ctl_seq, dc_f, dc_b, en, k, dedupe, revcom, Nf, Nb, min_count, n_seeds)
+        _, Nf, Nb = count_both(fg_seq, ctl_seq, dc_f, dc_b, k, dedupe, revcom, use_work=use_work)
+        (_, kh, a, b, z), _ = select_enriched(ctl_seq, dc_f, dc_b, en, k, dedupe, revcom, Nf, Nb, min_count, n_seeds, use_work=use_work)
     finally:
         for h in (en, dc_f, dc_b):
             if h is not None:
@@ -286,16 +376,22 @@ def select_seeds(fg_seq, ctl_seq, k, dedupe, revcom, min_count, n_seeds):
 
 
 def _discover_pwms(res_dir, control_fasta_file, seed_len=8, n_seeds=64, seed_mismatches=1, seed_count=20, flank=2, min_count=2,
-                   p_value=1e-4, pseudocount=1.0, revcom_mode=None, max_iter=20, min_overlap=5, family_e_value=0.01, output_dir=None):
+                   p_value=1e-4, pseudocount=1.0, revcom_mode=None, max_iter=20, min_overlap=5, family_e_value=0.01, output_dir=None,
+                   erase_rounds=1):
     """`kmap discover_pwms`: config.toml + the encoded reads of a preproc result directory + a control FASTA -> discovered_rank.csv,
     discover_trace.csv, matrices/seed{i}_{consensus}.csv and discovered.meme (the representatives: a --library_file for the library
     verbs) in output_dir (default res_dir/pwm_discovery).  Every argument and file is checked before the device is touched or
-    anything is written.  Under a torch.distributed launch rank 0 works alone.  Returns discover_core's results in seed order."""
+    anything is written.  Under a torch.distributed launch rank 0 works alone.  Returns discover_core's results in seed order.
+    erase_rounds above 1: discover_rounds -- after every round but the last the sites of the round's representatives are erased
+    from reads and control (DeviceSeq.erase_sites) and the next round takes its seeds and its counts from what is left; the two
+    tables get a `round` column and discover_erase.csv is written.  Every matrix is still evaluated on the original reads and the
+    original control, so mw_z is comparable between rounds -- and optimistic in every round, as without erasure."""
     from .kmer_count import encode_fasta, load_array_pickle, load_config, rank0_only, result_paths
     if not rank0_only():
         return None
     check_arguments(seed_len, n_seeds, seed_mismatches, seed_count, flank, min_count, p_value, pseudocount, max_iter, min_overlap,
-                    family_e_value)
+                    family_e_value, erase_rounds)
+    erase_rounds = int(erase_rounds)
     res, cfg_path, seq_path, border_path = result_paths(res_dir, reads=True)
     if control_fasta_file is None or not Path(control_fasta_file).is_file():
         raise ValueError(f"control FASTA file {control_fasta_file} is missing")
@@ -308,7 +404,9 @@ def _discover_pwms(res_dir, control_fasta_file, seed_len=8, n_seeds=64, seed_mis
     ctl_seq = None
     try:
         ctl_seq = DeviceSeq(*encode_fasta(str(control_fasta_file)))
-        seeds = select_seeds(fg_seq, ctl_seq, int(seed_len), dedupe, revcom, int(min_count), int(n_seeds))
+
+        def seeds_fn(r):
+            return select_seeds(fg_seq, ctl_seq, int(seed_len), dedupe, revcom, int(min_count), int(n_seeds), use_work=r > 1)
 
         def hist_fn(Ws, los, n_bins):
             per_set = []
@@ -318,16 +416,26 @@ def _discover_pwms(res_dir, control_fasta_file, seed_len=8, n_seeds=64, seed_mis
                     raise ValueError(f"discover_pwms: reads score outside the score range of seed {int(np.nonzero(outside)[0][0])}")
                 per_set += [hists, [ds.n_seq - int(s) for s in scored]]
             return tuple(per_set)
-        results = discover_core(seeds, lambda Ws, ts: fg_seq.library_counts(Ws, ts, revcom), hist_fn, match_motifs, revcom, int(flank),
-                                int(seed_mismatches), int(seed_count), p_value, float(pseudocount), int(max_iter), int(min_overlap),
-                                float(family_e_value))
+
+        def erase_fn(Ws, ts):
+            per_set = ()
+            for ds in (fg_seq, ctl_seq):
+                per_set += ds.erase_sites(Ws, ts, revcom, use_work=True)
+            return per_set
+        results, erase_log = discover_rounds(seeds_fn, lambda Ws, ts, use_work=False: fg_seq.library_counts(Ws, ts, revcom, use_work),
+                                             erase_fn, hist_fn, match_motifs, revcom, erase_rounds, int(flank), int(seed_mismatches),
+                                             int(seed_count), p_value, float(pseudocount), int(max_iter), int(min_overlap),
+                                             float(family_e_value))
     finally:
         for h in (ctl_seq, fg_seq):
             if h is not None:
                 h.close()
 
     out = res / OUTPUT_DIR if output_dir is None else Path(output_dir)
-    reps = write_discovery(out, results, float(pseudocount), revcom)
+    reps = write_discovery(out, results, float(pseudocount), revcom, erase_log if erase_rounds > 1 else None)
+    for e in erase_log:
+        print(f"round {e['round']}: {len(e['rows'])} {'matrix' if len(e['rows']) == 1 else 'matrices'} erased, {e['fg_new']} positions of the "
+              f"reads and {e['control_new']} of the control")
     for st in reps:
         print(f"{st['rank']} {st['name']} (seed {st['seed']}, family {st['family']} of {st['family_size']}): {st['status']} after "
               f"{st['iterations']} iteration{'s' if st['iterations'] != 1 else ''}, {st['n_selected']} sites ({st['n_minus']} on '-'), "

@@ -149,21 +149,23 @@ class DeviceEnrich:
 
 
 # ---- counting and selection of one k-mer length (enrich_kmers and discover_pwms) --------------------------------------------------
-def count_both(fg_seq, ctl_seq, dc_f, dc_b, k, dedupe, revcom):
-    """reads and control counted at length k into dc_f / dc_b, both merged with revcom: (n_fg_uniq, Nf, Nb)"""
-    n_fg = fg_seq.count(dc_f, k, dedupe, revcom, use_work=False)
+def count_both(fg_seq, ctl_seq, dc_f, dc_b, k, dedupe, revcom, use_work=False):
+    """reads and control counted at length k into dc_f / dc_b, both merged with revcom: (n_fg_uniq, Nf, Nb); use_work: under the
+    working masks of both sets instead of the original ones"""
+    n_fg = fg_seq.count(dc_f, k, dedupe, revcom, use_work=use_work)
     Nf = dc_f.total()
-    ctl_seq.count(dc_b, k, dedupe, revcom, use_work=False)       # merged like the foreground: the total and the ball masses
+    ctl_seq.count(dc_b, k, dedupe, revcom, use_work=use_work)    # merged like the foreground: the total and the ball masses
     Nb = dc_b.total()
     if max(Nf, Nb) > MAX_TOTAL or min(Nf, Nb) < 0:
         raise ValueError(f"k={k}: totals {Nf} / {Nb} outside 0..2^52 - 1")
     return n_fg, Nf, Nb
 
 
-def select_enriched(ctl_seq, dc_f, dc_b, en, k, dedupe, revcom, Nf, Nb, min_count, top_n):
+def select_enriched(ctl_seq, dc_f, dc_b, en, k, dedupe, revcom, Nf, Nb, min_count, top_n, use_work=False):
     """behind count_both: the device join, the z of every foreground k-mer with a count >= min_count and the exact selection of
-    the top_n best: (fetch()'s rows in rank order, n_control_uniq).  dc_b is counted again without the merge when revcom is set."""
-    n_ctl = ctl_seq.count(dc_b, k, dedupe, False, use_work=False) if revcom else dc_b.n_uniq     # B: unmerged, ascending
+    the top_n best: (fetch()'s rows in rank order, n_control_uniq).  dc_b is counted again without the merge when revcom is set
+    (use_work: under the control's working mask, as count_both counted it)."""
+    n_ctl = ctl_seq.count(dc_b, k, dedupe, False, use_work=use_work) if revcom else dc_b.n_uniq  # B: unmerged, ascending
     en.set_control(dc_b, revcom)
     en.run(dc_f, Nf, Nb, min_count)
     en.select(top_n)
