@@ -63,6 +63,14 @@ int kmap_memcpy2d_d2h(void *host_dst, size_t hpitch, const void *dev_src, size_t
  * keys) per device between calls.  kmap_scratch_release frees those of at least `min_bytes` on the current device (synchronises
  * it first); counts handles that were between kmap_counts_hist_packed_dev and kmap_counts_finish then fail with KMAP_E_STATE. */
 int kmap_scratch_release(size_t min_bytes);
+/* Test and diagnostic entries of that cache.  kmap_scratch_fill synchronises the current device and sets every cached buffer of
+ * it -- all streams, all slots, the whole allocation including the head-room behind the bytes last asked for -- to `byte`;
+ * *n_buffers / *n_bytes (either may be NULL) report what it set.  The shared histogram table is overwritten with the rest, so
+ * counts handles between kmap_counts_hist_packed_dev and kmap_counts_finish fail with KMAP_E_STATE as after a release.  No entry
+ * may depend on what the cache held before it was called, so a fill changes no result (tests/test_gpu_stale_state.py).
+ * kmap_scratch_acquired returns how many times the library has taken a buffer from the cache since it was loaded. */
+int kmap_scratch_fill(int byte, int64_t *n_buffers, int64_t *n_bytes);
+int kmap_scratch_acquired(int64_t *count);
 int kmap_stream_sync(void *stream);
 int kmap_stream_create(void **stream);
 int kmap_stream_destroy(void *stream);

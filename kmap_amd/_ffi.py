@@ -32,6 +32,8 @@ _SIGS = {
     "kmap_memcpy_d2d": (i32, [vp, vp, sz, vp]),
     "kmap_memcpy2d_d2h": (i32, [vp, sz, vp, sz, sz, sz, vp]),
     "kmap_scratch_release": (i32, [C.c_size_t]),
+    "kmap_scratch_fill": (i32, [i32, P(i64), P(i64)]),
+    "kmap_scratch_acquired": (i32, [P(i64)]),
     "kmap_stream_sync": (i32, [vp]),
     "kmap_stream_create": (i32, [P(vp)]),
     "kmap_stream_destroy": (i32, [vp]),

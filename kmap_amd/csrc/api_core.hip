@@ -23,12 +23,14 @@ struct Scratch {
 };
 std::mutex g_scratch_mu;
 std::map<std::tuple<int, void *, int>, Scratch> g_scratch;
+int64_t g_scratch_acquired = 0;   // calls of kmap_scratch so far (kmap_scratch_acquired), under g_scratch_mu
 }  // namespace
 
 int kmap_scratch(void **ptr, size_t bytes, hipStream_t stream, int slot) {
     int dev = 0;
     KMAP_CHECK_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(g_scratch_mu);
+    ++g_scratch_acquired;
     Scratch &sc = g_scratch[std::make_tuple(dev, (void *)stream, slot)];
     if (sc.bytes < bytes || !sc.p) {
         if (sc.p) {
@@ -73,6 +75,32 @@ static int scratch_release(size_t min_bytes) {
     return KMAP_OK;
 }
 
+// sets every cached buffer of the current device (all streams, all slots) to `byte` over its whole allocation, head-room included;
+// the device is synchronised before and after.  The shared bins table is overwritten like the rest, so its users are told as in
+// scratch_release
+static int scratch_fill(int byte, int64_t *n_buffers, int64_t *n_bytes) {
+    int dev = 0;
+    KMAP_CHECK_HIP(hipGetDevice(&dev));
+    KMAP_CHECK_HIP(hipDeviceSynchronize());
+    bool bins = false;
+    int64_t nb = 0, total = 0;
+    {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        for (auto &kv : g_scratch) {
+            if (std::get<0>(kv.first) != dev || !kv.second.p) continue;
+            KMAP_CHECK_HIP(hipMemset(kv.second.p, byte & 0xFF, kv.second.bytes));
+            bins = bins || std::get<2>(kv.first) == KMAP_SLOT_BINS;
+            ++nb;
+            total += (int64_t)kv.second.bytes;
+        }
+    }
+    KMAP_CHECK_HIP(hipDeviceSynchronize());
+    if (bins) kmap_counts_bins_invalidate(dev);
+    if (n_buffers) *n_buffers = nb;
+    if (n_bytes) *n_bytes = total;
+    return KMAP_OK;
+}
+
 int kmap_allow_lds(const void *kernel, int bytes) {
     static std::mutex mu;
     static std::map<std::pair<const void *, int>, int> done;     // (kernel, device) -> bytes granted
@@ -95,6 +123,13 @@ extern "C" {
 
 int kmap_version(void) { return 1000 * 0 + 1; }
 int kmap_scratch_release(size_t min_bytes) { return scratch_release(min_bytes); }
+int kmap_scratch_fill(int byte, int64_t *n_buffers, int64_t *n_bytes) { return scratch_fill(byte, n_buffers, n_bytes); }
+int kmap_scratch_acquired(int64_t *count) {
+    KMAP_REQUIRE(count, "kmap_scratch_acquired: null");
+    std::lock_guard<std::mutex> lock(g_scratch_mu);
+    *count = g_scratch_acquired;
+    return KMAP_OK;
+}
 const char *kmap_last_error(void) { return g_err; }
 
 int kmap_device_count(int *n) {

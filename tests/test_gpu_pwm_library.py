@@ -46,13 +46,11 @@ def check_against(got, want):
 
 
 # ---- 1. edges -----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def edge_set():
-    """~300 reads of lengths 0..200 (fixed seed) and: a read that begins in the last group of the first wave tile and ends in the
+def edge_reads():
+    """(seq, borders, Ws): ~300 reads of lengths 0..200 (fixed seed) and: a read that begins in the last group of the first wave tile and ends in the
     second tile, a read across three tiles, empty reads that share their start with the read behind them, 2 % invalid bases, n no
-    multiple of 16; the best window of matrix `minus` planted as its reverse complement only.  The model's scores per matrix are
-    computed once."""
-    from kmap_amd.motif_discovery import DeviceSeq
+    multiple of 16; the best window of matrix `minus` planted as its reverse complement only.  A plain function: the stale-state
+    cases of tests/test_gpu_stale_state.py run on the same reads."""
     rng = np.random.default_rng(1600)
     lengths, at = [], 0
     while 1015 - at > 210:                                   # random reads up to the first tile's end ...
@@ -89,6 +87,14 @@ def edge_set():
             seq[s + 20:s + 32] = 3 - top[::-1]
             n_planted += 1
     assert n_planted > 20
+    return seq, borders, Ws
+
+
+@pytest.fixture(scope="module")
+def edge_set():
+    """edge_reads() on the device; the model's scores per matrix are computed once"""
+    from kmap_amd.motif_discovery import DeviceSeq
+    seq, borders, Ws = edge_reads()
     scored = {k: window_scores(seq, W) for k, W in Ws.items()}
     ds = DeviceSeq(seq, borders)
     yield ds, seq, borders, Ws, scored
