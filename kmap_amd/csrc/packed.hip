@@ -11,7 +11,7 @@
 // Here: the layout itself -- pack / unpack, the hash materialisation and the prefix invalidation.  What works ON the layout lives by job:
 // the window-key front end in packed_keys.h, counting in counts_packed.hip (+ the per-read dedupe of dedupe_packed.hip, the partitioned
 // histograms of counts_part.hip / counts_fine.hip), the Hamming-ball mask and the occurrence scan in scan.hip (dispatch, k <= 16 ->
-// bitslice.hip) and scan_wide.hip (k > 16).
+// bitslice.hip, scan_reads.hip) and scan_wide.hip (k > 16).
 #include "common.h"
 #include "packed_keys.h"
 

@@ -1,8 +1,8 @@
 // scan.hip -- the handle of the per-read motif occurrence scan ("Hamming-ball scan over reads", BASELINE config 5; replaces
 // get_motif_occurence, reference motif_discovery.py:1422-1477): its result lists (reserve), their summary and the ways out of
 // the device (fetch) -- and, because they fill that handle, the two dispatching entry points of the verbs that run on the packed
-// reads: kmap_scan_run_packed_dev and kmap_mask_hamball_packed_dev check the arguments and hand over to bitslice.hip (k <= 16) or
-// scan_wide.hip (k > 16); the mask's coverage pass, which both branches end with, is here too.
+// reads: kmap_scan_run_packed_dev and kmap_mask_hamball_packed_dev check the arguments and hand over to bitslice.hip (k <= 16: the hit
+// bits of every window; the scan's per-read passes on them are scan_reads.hip) or scan_wide.hip (k > 16); the mask's coverage pass, which both branches end with, is here too.
 #include <algorithm>
 #include <vector>
 
@@ -214,7 +214,7 @@ int kmap_scan_fetch(kmap_scan *s, int32_t *hits_per_read, int8_t *min_dist, int3
 }
 
 // ---- the verbs on the packed reads ------------------------------------------------------------------------------------------------
-// k <= 16: the bit-sliced formulation (bitslice.hip) on the reads' bit planes; the per-window kernels of scan_wide.hip serve k > 16
+// k <= 16: the bit-sliced formulation (bitslice.hip, scan_reads.hip) on the reads' bit planes; the per-window kernels of scan_wide.hip serve k > 16
 static bool bitslice_on(int k) { return k <= 16; }
 
 int kmap_mask_hamball_packed_dev(const uint32_t *codes_dev, uint16_t *inval_dev, int64_t n, int k, const uint64_t *cons,

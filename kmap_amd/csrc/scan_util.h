@@ -1,5 +1,5 @@
 // scan_util.h -- small shared device utilities: the scans and sums inside a wave / a block, and the exclusive scan of an array of
-// uint32 counts (counts*.hip, scan_wide.hip, bitslice.hip, ...)
+// uint32 counts (counts*.hip, scan_wide.hip, scan_reads.hip, ...)
 #pragma once
 #include "common.h"
 

@@ -1,6 +1,7 @@
 // scan_wide.hip -- the Hamming-ball mask's flag pass and the occurrence scan for k > 16, window by window on the 2-bit packed reads
 // (layout: packed.hip; windows: packed_keys.h).  Nothing at k <= 16 runs these kernels: there both verbs are bit-sliced
-// (bitslice.hip).  The dispatching entry points are in scan.hip.
+// (bitslice.hip, the scan's per-read passes: scan_reads.hip).  The read geometry of the scan is scan_internal.h's, shared with
+// those passes.  The dispatching entry points are in scan.hip.
 #include "common.h"
 #include "packed_keys.h"
 #include "scan_internal.h"
@@ -42,14 +43,6 @@ __global__ __launch_bounds__(BLK) void mask_flag_packed_kernel(const uint32_t *_
 
 // ---- occurrence scan on the packed stream (get_motif_occurence, motif_discovery.py:1422-1477) ------------------------
 constexpr int SC_WAVES = 4;
-__device__ __forceinline__ int64_t slice_stop(int64_t L, int k) {
-    int64_t stop = L - k + 1;
-    if (stop < 0) {
-        stop += L;
-        if (stop < 0) stop = 0;
-    }
-    return stop > L ? L : stop;
-}
 __device__ __forceinline__ int pos_dist(const uint32_t *__restrict__ codes, const uint16_t *__restrict__ inval, int64_t p,
                                         int k, uint64_t kmask, uint64_t cons, uint64_t rcc, int revcom) {
     const Win w = load_win(codes, inval, p >> 4);
@@ -74,11 +67,8 @@ __global__ __launch_bounds__(KMAP_WAVE *SC_WAVES) void scan_packed_kernel(const 
     const int lane = threadIdx.x & 63;
     const int64_t s = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);
     if (s >= n_seq) return;
-    int64_t st = borders[2 * s], en = borders[2 * s + 1];
-    if (st < 0) st = 0;
-    if (en > n) en = n;
-    const int64_t L = en > st ? en - st : 0;
-    const int64_t stop = slice_stop(L, k);
+    const ReadSlice rs = read_slice(borders, 0, 0, s, n, k);
+    const int64_t st = rs.st, L = rs.L, stop = rs.stop;
     const uint64_t kmask = low_mask<uint64_t>(k);
     // the read's own end acts like a separator even if the caller's border does not sit on one
     constexpr int REG = 4;                       // distances kept in registers for reads up to 256 positions
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(KMAP_WAVE *SC_WAVES) void scan_packed_kernel(const 
 // ---- occurrence scan, flat formulation ---------------------------------------------------------------------------
 // The wave-per-read kernel above spends its time on per-read latency chains (borders -> codes -> reduce -> ballot): 10^7
 // waves of ~3 positions per lane.  Split instead into
-// (k > 16 only: k <= 16 scans the bit-sliced hit words of bitslice.hip.)
+// (k > 16 only: k <= 16 scans the bit-sliced hit words of bitslice.hip in scan_reads.hip.)
 //   (1) a flat pass, thread per 16-position group, that stores the capped distance of EVERY window as a nibble
 //       (d <= radius ? d : 15; 8 B per group = 0.5 B per position) -- independent of read borders because a window that
 //       the scan may use (p < L-k+1) lies entirely inside its read;
@@ -216,13 +206,10 @@ __global__ __launch_bounds__(FL_TPB) void scan_reads_kernel(const uint64_t *__re
     int64_t st = 0, stop = 0;
     bool quirk = false;
     if (s < n_seq) {
-        st = borders[2 * s];
-        int64_t en = borders[2 * s + 1];
-        if (st < 0) st = 0;
-        if (en > n) en = n;
-        const int64_t L = en > st ? en - st : 0;
-        quirk = (L - k + 1 < 0);                 // negative slice stop (motif_discovery.py:1443): every window runs off the read
-        stop = slice_stop(L, k);
+        const ReadSlice rs = read_slice(borders, 0, 0, s, n, k);
+        st = rs.st;
+        stop = rs.stop;
+        quirk = rs.quirk;                        // negative slice stop: every window runs off the read
     }
     int best = 15, count = 0;
     uint64_t base = 0;

@@ -1,6 +1,6 @@
 """GPU parity of the 2-bit-packed read path against the CPU oracle: pack/unpack round trip and window hashes for every k
 (packed.hip, packed_keys.h), histogram counting (counts_packed.hip, dedupe_packed.hip, counts_part / _fine / _range.hip),
-Hamming-ball masking (incl. the reference's invalid-hash quirk) and the occurrence scan (scan.hip -> bitslice.hip, scan_wide.hip).
+Hamming-ball masking (incl. the reference's invalid-hash quirk) and the occurrence scan (scan.hip -> bitslice.hip + scan_reads.hip, scan_wide.hip).
 Bit-exact."""
 import ctypes as C
 
@@ -232,6 +232,72 @@ def test_packed_scan_more_hits_than_the_one_pass_buffer(env):
             assert hits[i] == m
             np.testing.assert_array_equal(pos[offs[i]:offs[i + 1]], buf[:m])
     ds.close()
+
+
+def test_packed_scan_overflow_fallback_read_length_mix(env):
+    """The count / scan / write form (the fallback when a region of the one-pass buffer overflows) on every class of read: a first
+    block of 256 poly-A reads of 150 positions overflows its region (2^20 / 64 entries), so ALL reads are counted and written by
+    the two-pass kernels -- empty reads, the negative-slice quirk (shorter than k - 1), short reads on the chunked hit walk, reads
+    past 1024 windows on the whole-wave walk; random reads whose hits lie at several distances (the "mixed" flag that travels in
+    the min_dist byte between the two kernels), poly-A reads (ties at the minimum), reads with an invalid position in the middle,
+    and borders off the separators.  Three configurations: AAA at radius 1 on one strand, where an invalid window (all-ones hash,
+    TTT) is at distance 3 and no hit -- the kernel instances that never read the invalid mask; the same with the reverse
+    complement, where it is at distance 0; and poly-T at radius k -- the instances where invalid windows are hits themselves.
+    hits, positions and the minimum-distance byte of every read == oracle.  One kept divergence in the byte: a read shorter than
+    k - 1 whose negative slice is EMPTY has no window, the oracle says -1, and the kernels store the distance of the all-ones hash
+    when it lies within the radius (the count is 0 either way)."""
+    _ffi, _, DeviceSeq, O = env
+    rng = np.random.default_rng(2048)
+    region = (1 << 20) // 64
+    for k, cons, r, revcom, invalid_hits in ((3, int(O.kmer2hash("AAA")), 1, False, False), (3, int(O.kmer2hash("AAA")), 1, True, True),
+                                            (4, int(O.kmer2hash("TTTT")), 4, True, True)):
+        bases = [(cons >> (2 * j)) & 3 for j in range(k)]
+        d_inv = sum(x != 3 for x in bases)                         # the all-ones hash is poly-T; its reverse complement poly-A
+        if revcom:
+            d_inv = min(d_inv, sum(x != 0 for x in bases))
+        assert (d_inv <= r) == invalid_hits, (k, cons, r, revcom, d_inv)   # which instances the per-read kernels take
+        cycle = [0, 1, k - 2, k - 1, k, 63, 64, 65, 384, 385, 700, 1023 + k, 1024 + k, 1025 + k, 3000]
+        parts, borders, st = [], [], 0
+        for i in range(2048):
+            if i < 256:
+                rd = np.zeros(150, np.uint8)
+            else:
+                L, kind = cycle[(i - 256) % len(cycle)], ((i - 256) // len(cycle)) % 3
+                rd = rng.integers(0, 1 if kind == 1 else 4, size=L).astype(np.uint8)   # kind 1: poly-A
+                if kind == 2 and L:
+                    rd[L // 2] = 255
+            parts += [rd, np.array([255], np.uint8)]
+            borders.append((st, st + len(rd)))
+            st += len(rd) + 1
+        seq, borders = np.concatenate(parts), np.array(borders, np.int64)
+        sub = borders.copy()                                      # a second set of "reads": windows strictly inside the first
+        wide = (borders[:, 1] - borders[:, 0]) > 12
+        sub[wide, 0] += 3
+        sub[wide, 1] -= 2
+        borders = np.concatenate([borders, sub[wide]])
+        ds = DeviceSeq(seq, borders)
+        hits, pos = ds.scan(k, cons, r, revcom)
+        block = [int(hits[b:b + 256].sum()) for b in range(0, len(hits), 256)]
+        assert max(block) > region + 256, (k, revcom, max(block))  # more than a region holds: the fallback ran
+        h2, mind = np.empty(ds.n_seq, np.int32), np.empty(ds.n_seq, np.int8)
+        _ffi.check(_ffi.lib().kmap_scan_fetch(ds._scan, _ffi.ptr(h2), _ffi.ptr(mind), None))
+        np.testing.assert_array_equal(h2, hits)
+        buf, md, off, n_empty = np.empty(4096, np.int32), C.c_int(0), 0, 0
+        for i, (a, b) in enumerate(borders):
+            L = int(b - a)
+            m = O.lib().ko_scan_read(np.ascontiguousarray(seq[a:b]), L, k, cons, r, int(revcom), buf, C.byref(md))
+            assert hits[i] == m, (k, revcom, i, L, hits[i], m)
+            np.testing.assert_array_equal(pos[off:off + m], buf[:m])
+            empty_negative_slice = L - k + 1 < 0 and 2 * L - k + 1 <= 0
+            if empty_negative_slice and d_inv <= r:
+                assert m == 0 and md.value == -1 and mind[i] == d_inv, (k, revcom, i, L, mind[i])
+                n_empty += 1
+            else:
+                assert mind[i] == md.value, (k, revcom, i, L, mind[i], md.value)
+            off += m
+        assert off == len(pos)
+        assert (n_empty > 0) == invalid_hits
+        ds.close()
 
 
 def test_counting_full_size_properties(env):

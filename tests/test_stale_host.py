@@ -268,8 +268,7 @@ def test_rows_name_declared_cases_of_their_entries():
 
 
 # source files whose exported entries take no scratch although the file calls kmap_scratch or a helper that does
-NO_ROW = {"bitslice.hip": "its only exported entry packs the bit planes; its scratch is taken by helpers that scan.hip's entries call",
-          "api_core.hip": "the arena itself"}
+NO_ROW = {"api_core.hip": "the arena itself"}
 TAKERS = r"\bkmap_scratch\(|\bexclusive_scan_(u32|total)\b|\bradix_sort\(|\bpwm_pass_a\(|\bpwm_key_batches<"
 
 
